@@ -13,14 +13,20 @@ Inputs (2-bit packed contigs + records) are resident in HBM before timing.
 Multi-GPU (torchrun, one rank per GPU, the library's own RCCL communicator;
 no PyTorch in the process):
   default (strong) BASELINE configs[3]: config 3 itself (200k contigs, 100M
-                  fragments) divided over the N ranks; a weak leg follows under
-                  "weak" (--no-weak-leg skips it);
+                  fragments) divided over the N ranks; with --full a weak leg
+                  follows under "weak" (--no-weak-leg skips it);
   --weak          headline = weak scaling: rank r owns contig rows
                   [r*200k, (r+1)*200k) and fragments [r*100M, (r+1)*100M) of a
                   global problem whose genes span all ranks.
 The step adds the presence all-gather, the exception-key all-gather, the edge
 partial all-to-all-v (pre-reduced pairs routed to the owner of contig a) and
 the totals all-gather (karma_amd/distributed.py, karma_amd/comm.py).
+
+A plain run sets up, warms up, times --steps steps, writes the last timed
+step's outputs when --dump-outputs DIR is given, and prints the line.  --full
+adds every other measurement and check (per-kernel pass and roofline, in-run
+parity, single batch, other records format, end-to-end legs, CPU baseline,
+reference comparison, weak leg).
 
 Prints ONE JSON line on rank 0 (DESIGN.md §5 defines every field).
 """
@@ -53,7 +59,7 @@ CONFIGS = {
 }
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100,
@@ -84,8 +90,23 @@ def parse():
                          "u32 contig | read-start << 31: the graph depends only on which records share a read) or "
                          "pairs ({u32 read id, u32 contig}); the other format is timed too, as records_other")
     ap.add_argument("--no-other-format", action="store_true", help="skip the records_other leg")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline (set up, warm up, time the steps, print the line) also run everything "
+                         "else the line can report: the per-kernel timing pass with the roofline and write-ceiling "
+                         "figures, the in-run digest parity check, the single-batch latency, the other records "
+                         "format, the end-to-end, drop-in and eq-path legs, the CPU baseline, the comparison with the "
+                         "measured reference and (N > 1) the weak leg; --cpu-baseline and the --no-* options choose "
+                         "among them.  Without --full none of them runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's outputs (its profile, edges and readset "
+                         "totals, as the caller of the step receives them) to DIR/<name>.npy in float64, at most "
+                         "64 MB in all (a fixed, seeded sample of what is larger); inputs and samples depend only on "
+                         "the arguments, so two builds can be compared file by file")
+    a = ap.parse_args(argv)
     a.strong = not a.weak
+    if not a.full:
+        a.no_timing = a.no_e2e = a.no_parity = a.no_other_format = a.no_weak_leg = True
+        a.cpu_baseline = "off"
     return a
 
 
@@ -287,10 +308,12 @@ class Leg:
     def sync_all(self):
         self.build.sync()  # every enqueued step, deferred checks included, and the contexts
 
-    def timed(self, steps, warmup, kernel_timing=True):
+    def timed(self, steps, warmup, kernel_timing=True, keep_last=False):
         """W untimed steps, an optional per-kernel pass, then K steps bracketed by
         barrier + device sync; returns (max-over-ranks seconds, last result,
-        per-kernel totals, dominant kernel, its live (ms, launches))."""
+        per-kernel totals, dominant kernel, its live (ms, launches)).
+        keep_last (--dump-outputs with the Python step driver, whose steps
+        otherwise free their outputs): the last timed step keeps its own."""
         comm = self.comm
         # with the native step the timed batches are deferred ones (below): the
         # warm-up runs that same kind of step, so both main streams' tail
@@ -348,7 +371,7 @@ class Leg:
         # kernels run; only the host's readback moves behind the sync)
         for i in range(steps):
             h0 = time.perf_counter()
-            res = self.step(count=i == steps - 1 and not native)
+            res = self.step(count=i == steps - 1 and not native, keep=keep_last and i == steps - 1)
             host += time.perf_counter() - h0
             WATCHDOG.tick(f"timed step {i}")
         info_loop = self.build.native.info() if self.build.native is not None else None
@@ -439,6 +462,61 @@ class Leg:
         self.build.close()
         self.store.close()
         self.rec_dev.close()
+
+
+DUMP_BUDGET = 60 << 20  # --dump-outputs: bytes of array data over all files and ranks (64 MB with the headers)
+
+
+def _sample(n, limit, rng):
+    """All of range(n), or a sorted, seeded sample of at most `limit` of it."""
+    if n <= limit:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(rng.integers(0, n, max(1, limit)))
+
+
+def dump_outputs(leg, res, path):
+    """--dump-outputs: the last timed step's outputs as the timed loop left them
+    (called before anything else runs a step), float64 .npy files under `path`:
+      profile, profile_rows      the dense profile's sampled rows and their indices
+      edges_a, edges_b, edges_shared, edges_weight, edges_index
+                                 this rank's edges, sorted by (a, b), and their indices
+      totals, totals_index       the readset sizes and their indices
+      shape                      [profile rows, M, edges, totals] before sampling
+    With the native step they are read as parity_check reads them
+    (karma_step_profile, karma_step_newest_edges); with the Python driver the
+    last timed step kept them (Leg.timed keep_last).  What exceeds its share of
+    DUMP_BUDGET is sampled by indices that depend only on the sizes, so runs of
+    the same arguments write the same entries.  Ranks beyond the first write
+    <name>.rank<r>.npy."""
+    native = leg.build.native
+    if native is not None:
+        prof = native.profile()
+        e, _ = native.newest_edges()
+    else:
+        prof, e = res["profile"], res["edges"]
+    rng = np.random.default_rng(0x6B61726D)
+    budget = DUMP_BUDGET // leg.world
+    rows, M = prof.shape
+    ridx = _sample(rows, budget * 5 // 8 // (8 * M + 8), rng)
+    if len(ridx) == rows:
+        sample = prof.numpy()
+    else:
+        sample = np.empty((len(ridx), M), np.float64)
+        for i, r in enumerate(ridx.tolist()):
+            sample[i] = prof.view(r * M, M).numpy()
+    eidx = _sample(len(e.a), budget // 4 // 40, rng)
+    tidx = _sample(len(e.totals), budget // 8 // 16, rng)
+    out = {"profile": sample, "profile_rows": ridx,
+           "edges_a": e.a[eidx], "edges_b": e.b[eidx], "edges_shared": e.shared[eidx],
+           "edges_weight": e.weight[eidx], "edges_index": eidx,
+           "totals": e.totals[tidx], "totals_index": tidx,
+           "shape": np.array([rows, M, len(e.a), len(e.totals)])}
+    os.makedirs(path, exist_ok=True)
+    suffix = f".rank{leg.rank}.npy" if leg.rank else ".npy"
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + suffix), np.ascontiguousarray(arr, np.float64))
+    log(f"[rank {leg.rank}] wrote the last timed step's outputs to {path}: {len(ridx)} of {rows} profile rows x {M}, "
+        f"{len(eidx)} of {len(e.a)} edges, {len(tidx)} of {len(e.totals)} totals")
 
 
 def digest_key(args, world, emu):
@@ -625,9 +703,14 @@ def run(args, rank, world, local_rank, launcher):
     WATCHDOG.tick("inputs resident")
     inp, A = leg.inp, leg.A
     n_loc, f_loc = inp["n_loc"], inp["f_loc"]
-    dt, res, kern, dom, dom_live = leg.timed(args.steps, args.warmup, not args.no_timing)
+    dt, res, kern, dom, dom_live = leg.timed(args.steps, args.warmup, not args.no_timing,
+                                             keep_last=bool(args.dump_outputs) and leg.build.native is None)
+    if args.dump_outputs:
+        dump_outputs(leg, res, args.dump_outputs)
+        WATCHDOG.tick("outputs written")
     rec = inp["rec"]
-    n_reads = int(np.count_nonzero(rec[1:, 0] != rec[:-1, 0])) + 1 if A else 0
+    # (the compact reads: only the roofline's intermediate bytes need them)
+    n_reads = int(np.count_nonzero(rec[1:, 0] != rec[:-1, 0])) + 1 if A and dom_live else 0
 
     units = comm.sum_int(n_loc + f_loc) * args.steps
     value = units / dt
@@ -693,8 +776,10 @@ def run(args, rank, world, local_rank, launcher):
     if not args.no_parity:
         parity = parity_check(leg, digest_key(args, world, inp["emu"]))
         WATCHDOG.tick("parity")
-    single = leg.single_batch()
-    WATCHDOG.tick("single batch")
+    single = None
+    if args.full:
+        single = leg.single_batch()
+        WATCHDOG.tick("single batch")
     other = None
     # (not for a profile of tens of GB: the second build would hold its own buffers beside the first's)
     if not args.no_other_format and 8 * n_loc * M < (32 << 30):
@@ -730,7 +815,7 @@ def run(args, rank, world, local_rank, launcher):
 
     if rank == 0:
         emu = inp["emu"]
-        ref = reference_measured(args.config)
+        ref = reference_measured(args.config) if args.full else None
         line = {
             "metric": "contigs+reads/sec for k-mer vec + shared-read graph build; HBM GB/s vs roofline",
             "value": round(value, 1),
@@ -739,8 +824,9 @@ def run(args, rank, world, local_rank, launcher):
             "transport": transport,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(step_s * 1e3, 3),
-            "single_batch_ms": single["ms"],
+            "single_batch_ms": single["ms"] if single else None,
             "single_batch": single,
             "higher_is_better": True,
             "scaling": "strong" if args.strong else "weak",
@@ -777,6 +863,7 @@ def run(args, rank, world, local_rank, launcher):
             "step_driver": step_driver,
             "kernels_ms_per_step": {k: round(v[0] / args.steps, 4) for k, v in kern.items()},
             "kernels_ms_note": "sequential pass (profile on the main stream), every launch timed",
+            **({"outputs_dumped": args.dump_outputs} if args.dump_outputs else {}),
             **({"weak": weak} if weak else {}),
             **extra,
             "cpu_baseline": cpu,

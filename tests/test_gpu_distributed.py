@@ -221,7 +221,7 @@ def _bench_two_ranks(*extra, timeout=240):
 def test_bench_under_torch_distributed_run_two_ranks():
     """Rank 0 prints exactly one JSON line: the strong headline (BASELINE
     configs[3] shape) with the whole-job value, and the weak leg as an extra key."""
-    res = _bench_two_ranks("--steps", "2", "--warmup", "1", "--config", "tiny")
+    res = _bench_two_ranks("--full", "--steps", "2", "--warmup", "1", "--config", "tiny")
     assert res["n_gpus"] == 2 and res["steps"] == 2 and res["scaling"] == "strong"
     assert res["value"] > 0 and res["ms_per_step"] > 0
     assert res["weak"]["scaling"] == "weak" and res["weak"]["value"] > 0
@@ -235,8 +235,8 @@ def test_bench_strong_config3_two_ranks_in_run_parity():
     rank 0 combines them with the ranks' edges and totals) must match
     tests/golden/digests.json config3 -- the oracle's digests, which the
     reference's own config-3 outputs also match."""
-    res = _bench_two_ranks("--steps", "1", "--warmup", "1", "--no-weak-leg", "--no-timing", "--cpu-baseline", "off",
-                           timeout=600)
+    res = _bench_two_ranks("--full", "--steps", "1", "--warmup", "1", "--no-weak-leg", "--no-timing",
+                           "--cpu-baseline", "off", timeout=600)
     assert res["scaling"] == "strong" and res["config"]["contigs_rank0"] == 100_000
     d = res["parity_detail"]
     assert res["parity"] is True, d

@@ -10,7 +10,7 @@ for rep in ${REPS:-1 2}; do
       extra=""; case $leg in strong_emu*) extra="--emulate-ranks 8" ;; weak_emu*) extra="--weak --emulate-ranks 8" ;; esac
       # config3 uses h as given; emulated legs too (the default there is 1)
       f=$OUT/${leg}_${name}_r${rep}
-      KARMA_SIDE_HEADROOM=$hr KARMA_LIB=$lib KARMA_ALLOW_VARIANT=1 timeout -k 10 240 python bench.py --cpu-baseline off --no-e2e --no-parity --steps 30 $extra > $f.json 2> $f.err || { echo "$leg $name failed"; tail -5 $f.err; exit 1; }
+      KARMA_SIDE_HEADROOM=$hr KARMA_LIB=$lib KARMA_ALLOW_VARIANT=1 timeout -k 10 240 python bench.py --full --cpu-baseline off --no-e2e --no-parity --steps 30 $extra > $f.json 2> $f.err || { echo "$leg $name failed"; tail -5 $f.err; exit 1; }
       python -c "import json; d=json.load(open('$f.json')); print('$leg', '$name', 'rep', $rep, d['ms_per_step'], 'prof', d['kernels_ms_per_step']['kmer_profile'])"
     done
   done

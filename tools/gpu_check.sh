@@ -12,7 +12,7 @@ if [ -z "$SKIP_CONSUMERS" ]; then
 timeout -k 10 300 python tools/bench_consumers.py > $OUT/consumers_$TAG.json 2> $OUT/consumers_$TAG.err || { echo "consumers failed"; tail $OUT/consumers_$TAG.err; exit 1; }
 cat $OUT/consumers_$TAG.json
 fi
-timeout -k 10 300 python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { echo "bench failed"; tail $OUT/bench_$TAG.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { echo "bench failed"; tail $OUT/bench_$TAG.err; exit 1; }
 cat $OUT/bench_$TAG.json
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o trace --output-format csv -- \

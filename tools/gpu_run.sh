@@ -28,11 +28,11 @@ for item in "$@"; do
       TAIL=5 step $TAG/smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
       grep -q "smoke ok" $OUT/smoke.log || fail "smoke failed" ;;
     bench)
-      timeout -k 10 600 python bench.py $arg > $OUT/bench.json 2> $OUT/bench.err
+      timeout -k 10 600 python bench.py --full $arg > $OUT/bench.json 2> $OUT/bench.err
       rc=$?; echo "bench rc=$rc"; [ $rc -ne 0 ] && { tail -5 $OUT/bench.err; exit $rc; }
       python tools/summarize_bench.py $OUT/bench.json ;;
     ranks2)
-      KARMA_FORCE_DEVICE=0 KARMA_DIST_BACKEND=host timeout -k 10 600 python bench.py --gpus 2 --cpu-baseline off \
+      KARMA_FORCE_DEVICE=0 KARMA_DIST_BACKEND=host timeout -k 10 600 python bench.py --full --gpus 2 --cpu-baseline off \
           --no-e2e --no-weak-leg $arg > $OUT/ranks2.json 2> $OUT/ranks2.err
       rc=$?; echo "ranks2 rc=$rc"; [ $rc -ne 0 ] && { tail -8 $OUT/ranks2.err; exit $rc; }
       python tools/summarize_bench.py $OUT/ranks2.json ;;
