@@ -229,7 +229,11 @@ typedef struct karma_pairs karma_pairs;
 #define KARMA_REC_FLAGGED 2  /* records as n_records x u32: contig | (first record of its read) << 31, grouped by
                               * read.  The graph depends only on which records share a read (read_graph.py:31-49
                               * intersects readsets), so the read ids give way to read-start flags: 4 bytes per
-                              * record instead of 8.  Record 0 always starts a read; contig ids < 2^31. */
+                              * record instead of 8.  Record 0 always starts a read; contig ids < 2^31.
+                              * The words no longer carry read ids, so the format itself cannot be checked for
+                              * grouping (records of ids A, B, A are three reads here, where KARMA_REC_SORTED
+                              * reports KARMA_ERR_UNSORTED): whoever makes the words checks it, as
+                              * karma_amd.engine.flag_records does (ValueError when read ids decrease). */
 /* records: n_records x {u32 read_id, u32 contig} interleaved (or, flags =
  * KARMA_REC_FLAGGED, n_records x u32 flagged contigs; records is then a
  * uint32_t array of n_records entries).  Deduplicates
@@ -366,7 +370,17 @@ typedef struct karma_step karma_step;
 #define KARMA_STEP_DEFER 4      /* outputs not read: the step returns without waiting for anything (its
                                  * checks arrive through mapped memory and are read <= 3 steps later; a
                                  * step needing the general path runs again synchronously; a status later
-                                 * than KARMA_STEP_STALL_S seconds (120) is KARMA_ERR_STALL).  Several ranks:
+                                 * than KARMA_STEP_STALL_S seconds (120) is KARMA_ERR_STALL).  A status is
+                                 * read only at points the call sequence fixes, never because it has
+                                 * already landed: by the third deferred step after its own (which waits
+                                 * for it), by the next synchronous step -- one of the 8 deferred calls
+                                 * that run synchronously after a re-run included, which checks every
+                                 * pending step -- and by karma_step_sync.  The counters of
+                                 * karma_step_info therefore follow from the order of calls alone.
+                                 * records_dev must be 16-byte aligned (without KARMA_STEP_KEEP; checked
+                                 * on entry, before any state changes, whether or not the call ends up
+                                 * deferred: KARMA_ERR_ARG); other steps take any 4-byte (flagged) or
+                                 * 8-byte aligned pointer and copy when they must.  Several ranks:
                                  * once a synchronous step has sized the
                                  * exchange's slots and the store is ACGT-only on every rank (else the
                                  * step runs synchronously, its edge count not read back); every rank

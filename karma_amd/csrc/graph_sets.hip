@@ -216,7 +216,7 @@ __device__ __forceinline__ int rank_below(unsigned long long m) {
 //     "head" (the records before that lane's first read start): the next lane
 //     receives the tail (DPP) and emits the merged read; lane 63's tail is
 //     carried into the next step's lane 0, and after the chunk's last step
-//     into a tail-only pass over the next 8 records;
+//     into a tail-only pass over the next 8 records (16 with 16 per lane);
 //   * a read longer than 8 records (a tail plus a head of > 8 records, or a
 //     lane without any read start) goes to the big-read list from the lane
 //     that merges its tail.
@@ -1022,11 +1022,13 @@ classify2_kernel(ClassArgs P, BinArgs Q) {
         prev_rid = s_rid;
     }
     // the chunk's last tail read continues into the next chunk's first records
-    // (at most 8 of them matter): uniform scalar walk
+    // (at most 8 of them matter; 16 with 16 records per lane, where a compact
+    // read is a code whatever its length): uniform scalar walk
     if (ct_ok) {
         RState h{};
         uint32_t hl = 0;
-        for (; hl < (uint32_t)kMaxFast && c_hi + hl < P.A; ++hl) {
+        constexpr uint32_t kWalk = RPL > 8 ? (uint32_t)RPL : (uint32_t)kMaxFast;
+        for (; hl < kWalk && c_hi + hl < P.A; ++hl) {
             uint32_t y;
             if (FLAG) {
                 const uint32_t w = P.recw[c_hi + hl];
@@ -1041,9 +1043,16 @@ classify2_kernel(ClassArgs P, BinArgs Q) {
             if (hl == 0) rs_reset(h, cy);
             else rs_add(h, cy);
         }
-        const bool big = ct_len + hl > (uint32_t)kMaxFast;
-        uint32_t code;
-        const bool ok = !big && (hl ? rs_code2<COMPACT>(ct, h, P.N, &code) : rs_code<COMPACT>(ct, P.N, &code));
+        // 8 records per lane: big when longer than 8 records.  16: as inside the
+        // chunk (the walk's `big`) -- a read seen whole is a code when compact,
+        // whatever its length, and big only when it is general and longer than 8
+        // records, or when the walk met no read start within a lane's worth of
+        // records (its length is unknown here)
+        uint32_t code = 0;
+        const bool compact = hl ? rs_code2<COMPACT>(ct, h, P.N, &code) : rs_code<COMPACT>(ct, P.N, &code);
+        const bool big = RPL > 8 ? hl == kWalk || (!compact && ct_len + hl > (uint32_t)kMaxFast)
+                                 : ct_len + hl > (uint32_t)kMaxFast;
+        const bool ok = !big && compact;
         // lane 0's code (uniform values), in the staged form m0 << 4 | M << 1 | 1
         if (BIN && ok) {
             const uint32_t rel = (code >> 24) << 1 | 1u;

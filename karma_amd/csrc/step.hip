@@ -993,20 +993,22 @@ bool entry_done(const karma_step* s, uint64_t seq) {
     return __atomic_load_n(&s->ring_h[seq % kRing].seq, __ATOMIC_ACQUIRE) == seq;
 }
 
-// Checks deferred steps: every finished one (wait = false), or all of them
-// after waiting (wait = true), or down to kLag - 1 outstanding (lag = true).
+// Checks deferred steps: all of them (wait = true), or down to kLag - 1
+// outstanding (wait = false), waiting for each status it reads.  A status is
+// read only at points the call sequence fixes -- the lag point of a deferred
+// step, the start of a synchronous step (a sticky one included), and
+// karma_step_sync -- never because it happened to have landed: which steps
+// run deferred, which run again and which use their tail's own control block
+// then follow from the order of calls alone, on one process as on several
+// (where a re-run issues collectives, so every rank must read at the same point).
 // A step whose words call for the general path runs again synchronously;
 // the newest deferred step's profile, M and E stay the ones karma_step_sync
 // and karma_step_profile report (a re-run of an older step does not replace them).
-int drain(karma_step* s, bool wait, bool lag) {
+int drain(karma_step* s, bool wait) {
     while (!s->pending.empty()) {
         karma_step::Pending p = s->pending.front();
-        const bool must = wait || (lag && (int)s->pending.size() >= s->lag);
-        // several processes: a step's entry is read at the same point of the
-        // step sequence on every rank (a rerun issues collectives)
-        if (s->world > 1 && !must) break;
+        if (!wait && (int)s->pending.size() < s->lag) break;
         if (!entry_done(s, p.seq)) {
-            if (!must) break;
             // the main stream reaches the status kernel within a step's time
             const auto w0 = std::chrono::steady_clock::now();
             for (int spin = 0; !entry_done(s, p.seq); ++spin) {
@@ -1145,7 +1147,6 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
     RecIn rin;
     if (flg) rin.fw = rec;
     else rin.pr = reinterpret_cast<const uint2*>(rec);
-    KARMA_CHECK(!(reinterpret_cast<uintptr_t>(rec) & 15), KARMA_ERR_ARG, "karma_step_run: records must be 16-byte aligned");
     const int jrc = sets_begin_deferred(ctx, rin, A, s->n_glob, &job, &v);
     ctx->job_ctrl = nullptr;
     ctx->job_ctrl_words = 0;
@@ -1421,6 +1422,12 @@ int karma_step_run(karma_step* s, karma_contigs* store, const uint32_t* records,
     KARMA_CHECK((flags & ~(KARMA_STEP_KEEP | KARMA_STEP_SEQUENTIAL | KARMA_STEP_DEFER | KARMA_STEP_FLAGGED)) == 0,
                 KARMA_ERR_ARG,
                 "karma_step_run: unknown flags %d", flags);
+    // the deferred records job reads 16-byte words: checked here, before any
+    // counter, sequence number or context field changes, and whether or not
+    // this call ends up deferred (sticky steps, several ranks)
+    const bool defer_asked = (flags & KARMA_STEP_DEFER) && !(flags & KARMA_STEP_KEEP);
+    KARMA_CHECK(!defer_asked || !(reinterpret_cast<uintptr_t>(records) & 15), KARMA_ERR_ARG,
+                "karma_step_run: KARMA_STEP_DEFER records must be 16-byte aligned");
     karma_ctx* ctx = s->ctx;
     KARMA_TRY(ctx_begin(ctx));
     int64_t n_store = 0;
@@ -1443,13 +1450,16 @@ int karma_step_run(karma_step* s, karma_contigs* store, const uint32_t* records,
     int rc = KARMA_OK;
     if (defer && s->sticky_sync > 0) {
         --s->sticky_sync;
-        rc = drain(s, false, true);
+        // every deferred step still pending is checked now (this step waits for
+        // the device anyway): none lingers, with the caller's pointers, across
+        // the sticky steps, and a check is never read more than kLag steps late
+        rc = drain(s, true);
         if (!rc) rc = run_sync(s, store, records, n_records, flg, false, seq, false);
     } else if (defer) {
-        rc = drain(s, false, true);
+        rc = drain(s, false);
         if (!rc) rc = run_deferred(s, store, records, n_records, flg, seq);
     } else {
-        rc = drain(s, true, false);  // earlier deferred steps complete and checked first
+        rc = drain(s, true);  // earlier deferred steps complete and checked first
         if (!rc) rc = run_sync(s, store, records, n_records, flg, keep, seq, !(flags & KARMA_STEP_DEFER));
     }
     ctx->stream = prev;
@@ -1470,7 +1480,7 @@ int karma_step_sync(karma_step* s) {
     KARMA_TRY(ctx_begin(ctx));
     hipStream_t prev = ctx->stream;
     ctx->stream = s->main_s;
-    int rc = drain(s, true, false);
+    int rc = drain(s, true);
     ctx->stream = prev;
     KARMA_TRY(rc);
     KARMA_HIP(hipStreamSynchronize(s->side_s));

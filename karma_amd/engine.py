@@ -697,10 +697,15 @@ def flag_records(records):
     """(read, contig) records grouped by read -> KARMA_REC_FLAGGED words (the
     read ids replaced by read-start flags): contig | (first record of its read) << 31.
     The graph depends only on which records share a read, so the two formats
-    give the same graph."""
+    give the same graph.  Read ids that decrease (records not grouped by read:
+    ids A, B, A would become three reads) are a ValueError, the condition the
+    pairs format reports as KARMA_ERR_UNSORTED; the flagged words themselves no
+    longer carry the ids, so nothing downstream can check it."""
     rec = np.asarray(records, np.uint32).reshape(-1, 2)
     if len(rec) and int(rec[:, 1].max()) >= 1 << 31:
         raise ValueError("flagged records hold contig ids < 2^31")
+    if len(rec) > 1 and bool((rec[1:, 0] < rec[:-1, 0]).any()):
+        raise ValueError("records are not grouped by read (read ids decrease)")
     out = rec[:, 1].copy()
     if len(rec):
         start = np.empty(len(rec), np.uint32)

@@ -20,6 +20,7 @@ from karma_amd.contig import Contig
 from karma_amd.kmer import KmerClustering
 from karma_amd.read_graph import ReadGraph
 from oracle import oracle
+from record_layouts import chunk_edge_records
 
 pytestmark = pytest.mark.gpu
 
@@ -105,6 +106,36 @@ def test_profile_long_contigs_and_large_k8_columns():
     assert len(cols) > 36 * 1024
     assert cols == ocols
     assert np.array_equal(prof.view(np.uint64), oprof.view(np.uint64))
+
+
+@pytest.mark.parametrize("L", [65_535, 65_536])  # the last u16 case, the first u32 case
+@pytest.mark.parametrize("kmer", [1, 2, 5, "5p6"])
+def test_profile_u16_counters_at_their_limit(kmer, L):
+    """profile_wave_kernel packs two u16 counters per u32 while every contig is
+    shorter than 2^16 bases (kmer.hip C16), right only because a count is at
+    most L.  Long contigs at that limit put maximal counts into one counter
+    (poly-A: at k = 1 and L = 65,535 the count is 0xFFFF exactly) and
+    near-maximal ones into counters of neighbouring columns, the two halves of
+    one u32 (AC repeated; half poly-A, half poly-C), among 200 short contigs.
+    Each long contig stands first, in the middle and last once (a wave
+    strides over contigs).  Bit-exact against the oracle: profile, columns,
+    row totals."""
+    blob, offs, _ = engine.synth_contigs(88, 200, 30, 870, 300)
+    short = [(f">ctg{i}", bytes(blob[offs[i]:offs[i + 1]]).decode()) for i in range(200)]
+    long_ = [(">polyA", "A" * L), (">AC", ("AC" * (L // 2 + 1))[:L]), (">halves", "A" * (L // 2) + "C" * (L - L // 2))]
+    assert all(len(s) == L for _, s in long_)
+    for rot in range(3):
+        first, mid, last = (long_[(rot + i) % 3] for i in range(3))
+        seqs = OrderedDict([first] + short[:100] + [mid] + short[100:] + [last])
+        assert len(seqs) == 203
+        prof, cols, tot = engine.kmer_profile(seqs, kmer)
+        oprof, ocols, ocounts = oracle.calc_kmer_profile(seqs, kmer)
+        assert cols == ocols
+        assert prof.shape == oprof.shape
+        assert np.array_equal(prof.view(np.uint64), oprof.view(np.uint64)), (rot, kmer, L)
+        assert np.array_equal(tot, ocounts.sum(axis=1))
+        if kmer == 1:  # the count the test is about did occur: L x 'A' in the poly-A row
+            assert int(ocounts[list(seqs).index(">polyA")].max()) == L
 
 
 def test_profile_unsupported_k_raises():
@@ -341,6 +372,14 @@ def test_flagged_records_first_flag_and_chunk_edges():
         p.close()
         q.close()
         buf.close()
+
+
+def test_records_compact_reads_of_9_to_16_at_chunk_edges():
+    """Compact reads of 9, 12 and 16 records ending at, straddling and starting
+    at every multiple of 4,096 records (tests/record_layouts.py; the deferred
+    step's view of it: test_gpu_step.py), in both record formats."""
+    rec, _ = chunk_edge_records()
+    check_records(rec, 3000)
 
 
 @pytest.mark.parametrize("n", [3000, 1_200_000, 2_200_000])  # binned, compact unbinned, no compact path

@@ -18,6 +18,7 @@ from karma_amd import _lib, engine
 from karma_amd.comm import SoloComm
 from karma_amd.distributed import ShardedBuild
 from oracle import oracle
+from record_layouts import chunk_edge_records
 
 pytestmark = pytest.mark.gpu
 
@@ -89,7 +90,11 @@ def test_deferred_steps_then_kept_step_match_oracle(emulate, n_rate, flagged):
         calls = (_lib.api_calls() - calls0) / 4
         r.build.sync()
         info = r.build.native.info()
-        assert info[5] == 5 and info[6] == 0, info  # 5 deferred steps, none run again
+        # 5 deferred calls, then sync; nothing is slow, so no step runs again
+        # and none runs synchronously.  Steps 1 and 2 are the first jobs of
+        # the two main streams' tails (they size the tail's control block),
+        # steps 3..5 take it: 3 on their own block.
+        assert info[[4, 5, 6, 14]].tolist() == [0, 5, 0, 3], info.tolist()
         # the newest deferred step's profile (M read by the kernels on the device)
         prof_o, cols_o = oracle_profile(r.blob, r.offs, 0, r.n_loc)
         assert info[1] is not None
@@ -147,9 +152,19 @@ def test_deferred_steps_slow_path_runs_again(big, flagged):
             r.step(count=False)
         r.build.sync()
         info = r.build.native.info()
-        assert info[6] >= 1, info  # run again on the general path
-        if not big:
-            assert info[14] >= 1, info  # some verdicts came from the votes on the step's own block
+        if big:
+            # 3 deferred calls (none reaches the lag point: 3 pending), then
+            # sync reads all three: each is slow and runs again (3 synchronous
+            # steps).  Step 3 is the second job of its tail: 1 own block.
+            assert info[[4, 5, 6, 14]].tolist() == [3, 3, 3, 1], info.tolist()
+        else:
+            # calls 1..3 deferred; call 4 is the lag point of step 1 (waits for
+            # it: slow, it runs again, sticky = 8) and still runs deferred; call
+            # 5 is sticky: it checks steps 2..4 (all slow: 3 more re-runs) and
+            # runs synchronously, as do calls 6..12.  4 deferred, 4 re-run,
+            # 4 + 8 synchronous; steps 3 and 4 ran on their tail's own block,
+            # so their verdicts came from classify's votes, not from the probe.
+            assert info[[4, 5, 6, 14]].tolist() == [12, 4, 4, 2], info.tolist()
         res = r.step(keep=True)
         check_edges(res["edges"], oracle_graph(rec, n))
     finally:
@@ -167,7 +182,10 @@ def test_deferred_steps_on_own_control_block_launch_no_probe():
         for _ in range(3):
             r.step(count=False)  # each main stream's first job sizes its control block
         r.build.sync()
-        own0 = int(r.build.native.info()[14])
+        info0 = r.build.native.info()
+        # steps 1 and 2 size their tails' blocks, step 3 takes its tail's
+        assert info0[[4, 5, 6, 14]].tolist() == [0, 3, 0, 1], info0.tolist()
+        own0 = int(info0[14])
         r.ctx.timing(True, "relabel_probe")
         r.ctx.timing_reset()
         for _ in range(6):
@@ -178,7 +196,8 @@ def test_deferred_steps_on_own_control_block_launch_no_probe():
         info = r.build.native.info()
         assert int(info[14]) - own0 == 6, info
         assert probes == 0, probes
-        assert info[6] == 0, info
+        # 3 + 6 deferred calls, nothing slow: none synchronous, none run again
+        assert info[[4, 5, 6, 14]].tolist() == [0, 9, 0, 7], info.tolist()
         res = r.step(keep=True)
         check_edges(res["edges"], oracle_graph(rec, n))
     finally:
@@ -195,7 +214,10 @@ def test_deferred_step_bucket_overflow_runs_again():
     try:
         r.step(count=False)
         r.build.sync()
-        assert r.build.native.info()[6] == 1
+        # one deferred call (its tail's first job: not on an own block); sync
+        # reads its status: slow, it runs again (the one synchronous step)
+        info = r.build.native.info()
+        assert info[[4, 5, 6, 14]].tolist() == [1, 1, 1, 0], info.tolist()
         res = r.step(keep=True)
         check_edges(res["edges"], oracle_graph(rec, 1000))
     finally:
@@ -268,7 +290,10 @@ def test_two_steps_on_one_context_keep_their_own_status():
         for b, st, d, rec, n, blob, offs in runs:
             b.sync()
             info = b.native.info()
-            assert info[5] == 4 and info[6] == 0, info.tolist()  # 4 deferred, none run again
+            # per step object: 4 deferred calls (the 4th waits for the 1st's
+            # status at its lag point), then sync; nothing slow.  Steps 3 and
+            # 4 are the second jobs of their tails: 2 on their own block.
+            assert info[[4, 5, 6, 14]].tolist() == [0, 4, 0, 2], info.tolist()
             prof_o, cols_o = oracle_profile(blob, offs, 0, n)
             assert int(info[0]) == len(cols_o)
             assert int(info[1]) == len(oracle_graph(rec, n)["a"])
@@ -299,7 +324,10 @@ def test_middle_deferred_step_rerun_keeps_newest_outputs():
         r.step(count=False)
         r.build.sync()
         info = r.build.native.info()
-        assert info[6] == 1, info.tolist()  # the middle step ran again
+        # 3 deferred calls, then sync reads all three: only the middle step is
+        # slow and runs again (1 synchronous).  Step 3 is the second job of
+        # step 1's tail, with the same records: 1 on its own block.
+        assert info[[4, 5, 6, 14]].tolist() == [1, 3, 1, 1], info.tolist()
         e_new = len(oracle_graph(rec, n)["a"])
         assert len(oracle_graph(rec_big, n)["a"]) != e_new  # the big reads add edges
         assert int(info[1]) == e_new, (info.tolist(), e_new)
@@ -333,12 +361,135 @@ def test_failed_deferred_step_leaves_control_block_zeroed(monkeypatch, fault_seq
         assert failed == 1
         r.build.sync()
         info = r.build.native.info()
-        assert info[6] == 0, info.tolist()  # no stale flag asked for a re-run
+        # fault_seq + 4 deferred calls (the failed one counted: it fails after
+        # its records job), none slow: no stale flag asked for a re-run.  Every
+        # step from the 3rd on, the failed one included, took its tail's block.
+        assert info[[4, 5, 6, 14]].tolist() == [0, fault_seq + 4, 0, fault_seq + 2], info.tolist()
         o = oracle_graph(rec, n)
         e, deferred = r.build.native.newest_edges()
         assert deferred
         check_edges(e, o)
         prof_o, _ = oracle_profile(r.blob, r.offs, 0, n)
         assert np.array_equal(r.build.native.profile().numpy().view(np.uint64), prof_o.view(np.uint64))
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("sticky", [False, True])
+@pytest.mark.parametrize("flagged", [False, True])
+def test_misaligned_deferred_records_refused_before_any_state_change(flagged, sticky):
+    """KARMA_STEP_DEFER records must be 16-byte aligned: a misaligned pointer
+    is KARMA_ERR_ARG on entry, before any counter, sequence number or field of
+    the shared context changes -- karma_step_info is unchanged, a records job
+    on the same context and the next steps stay bit-exact.  sticky: the same
+    call while deferred calls run synchronously after a re-run (where the
+    synchronous path would have copied the pointer): acceptance does not
+    depend on that hidden state."""
+    n = 3000
+    rec = np.ascontiguousarray(engine.synth_records(SEED, n, 0, 100_000, True))
+    r = Run(n, rec, flagged=flagged)
+    d_big = None
+    try:
+        if sticky:
+            rng = np.random.default_rng(9)
+            r0 = int(rec[-1, 0]) + 1
+            big = np.array([(r0 + i, int(c)) for i in range(50) for c in rng.integers(0, n, 12)], np.uint32)
+            rec_big = np.concatenate([rec, big])
+            d_big = _lib.DevBuf.from_numpy(r.ctx, engine.flag_records(rec_big) if flagged
+                                           else rec_big.view(np.int64).reshape(-1))
+            r.build.run(r.store, d_big.ptr, len(rec_big), count=False)
+            r.build.sync()  # reads the step's status: big reads, it runs again; the next 8 deferred calls are sticky
+        for _ in range(3):
+            r.step(count=False)
+        info0 = r.build.native.info()
+        # not sticky: 3 deferred calls, the third on its tail's own block.
+        # sticky: 1 deferred call, re-run at sync (1 synchronous), then 3 sticky
+        # calls run synchronously; no job on an own block.
+        assert info0[[4, 5, 6, 14]].tolist() == ([4, 1, 1, 0] if sticky else [0, 3, 0, 1]), info0.tolist()
+        with pytest.raises(_lib.KarmaError) as ei:
+            r.build.run(r.store, r.dev.ptr + (4 if flagged else 8), len(rec) - 1, count=False)
+        assert ei.value.code == _lib.KARMA_ERR_ARG
+        assert np.array_equal(r.build.native.info(), info0), (r.build.native.info().tolist(), info0.tolist())
+        # the step is alive and may have deferred steps in flight: a records
+        # job on its context finds none of the step's scheduling state there
+        o = oracle_graph(rec, n)
+        check_edges(engine.graph_from_records(engine.flag_records(rec) if flagged else rec, n, ctx=r.ctx,
+                                              flagged=flagged), o)
+        for _ in range(3):
+            r.step(count=False)
+        r.build.sync()
+        info = r.build.native.info()
+        # not sticky: 3 more deferred calls, each on its tail's own block, none
+        # slow.  sticky: 3 more sticky calls run synchronously.
+        assert info[[4, 5, 6, 14]].tolist() == ([7, 1, 1, 0] if sticky else [0, 6, 0, 4]), info.tolist()
+        e, deferred = r.build.native.newest_edges()
+        assert deferred == (not sticky)
+        check_edges(e, o)
+        prof_o, _ = oracle_profile(r.blob, r.offs, 0, n)
+        assert np.array_equal(r.build.native.profile().numpy().view(np.uint64), prof_o.view(np.uint64))
+    finally:
+        if d_big is not None:
+            d_big.close()
+        r.close()
+
+
+@pytest.fixture(scope="module")
+def edge_layout():
+    rec, placed = chunk_edge_records()
+    return rec, placed, oracle_graph(rec, 3000)
+
+
+def test_chunk_edge_layout_places_every_read_kind(edge_layout):
+    rec, placed, _ = edge_layout
+    assert len(rec) == 40_000 and len(placed) == 9
+    assert sorted((m, pos) for _, m, pos in placed) == sorted((m, pos) for m in (9, 12, 16) for pos in "abc")
+    for i, (start, m, pos) in enumerate(placed):
+        edge = 4096 * (i + 1)
+        ids = rec[start:start + m, 0]
+        assert (ids == ids[0]).all() and rec[start - 1, 0] != ids[0] and rec[start + m, 0] != ids[0]
+        assert int(rec[start:start + m, 1].max()) - int(rec[start:start + m, 1].min()) <= 3  # compact
+        past = start + m - edge
+        assert {"a": past == 0, "b": 1 <= past <= 7, "c": past == m}[pos], (start, m, pos)
+
+
+def test_flagged_compact_reads_at_chunk_edges_stay_deferred(edge_layout):
+    """Flagged records hold 16 per lane, so a compact read of 9..16 records is
+    a code inside a chunk; the same read ending at, straddling or starting at a
+    chunk edge (classify's chunk-end tail walk) must be one too -- not a big
+    read, which would send every deferred step through a synchronous re-run."""
+    rec, _, o = edge_layout
+    r = Run(3000, rec, flagged=True)
+    try:
+        for _ in range(3):
+            r.step(count=False)
+        r.build.sync()
+        info = r.build.native.info()
+        # 3 deferred calls, then sync; nothing slow; step 3 on its tail's own block
+        assert info[[4, 5, 6, 14]].tolist() == [0, 3, 0, 1], info.tolist()
+        e, deferred = r.build.native.newest_edges()
+        assert deferred
+        check_edges(e, o)
+    finally:
+        r.close()
+
+
+def test_flagged_wide_read_at_chunk_edge_runs_again():
+    """The positive control of the test above: the same layout with one edge
+    read made wide (12 records over 200 contig ids: general and longer than 8
+    records, a big read) does ask for the re-run; results stay exact."""
+    rec, placed = chunk_edge_records(wide_edge=4)
+    assert placed[4][1:] == (12, "b")
+    r = Run(3000, rec, flagged=True)
+    try:
+        for _ in range(3):
+            r.step(count=False)
+        r.build.sync()
+        info = r.build.native.info()
+        # 3 deferred calls, then sync reads all three: each holds the big read
+        # and runs again (3 synchronous steps); step 3 on its tail's own block
+        assert info[6] >= 1, info.tolist()
+        assert info[[4, 5, 6, 14]].tolist() == [3, 3, 3, 1], info.tolist()
+        e, deferred = r.build.native.newest_edges()
+        check_edges(e, oracle_graph(rec, 3000))
     finally:
         r.close()
