@@ -104,7 +104,7 @@ int ctx_job_pinned(karma_ctx* ctx, size_t bytes, void** out) {
     return KARMA_OK;
 }
 
-int resident_grid(karma_ctx* ctx, const void* kernel, int block, size_t lds, int64_t work) {
+int resident_grid(karma_ctx* ctx, const void* kernel, int block, size_t lds, int64_t work, int headroom) {
     const auto key = std::make_pair(kernel, std::make_pair(block, lds));
     auto it = ctx->occupancy.find(key);
     int per_cu = 0;
@@ -115,18 +115,18 @@ int resident_grid(karma_ctx* ctx, const void* kernel, int block, size_t lds, int
             per_cu = 1;
         ctx->occupancy.emplace(key, per_cu);
     }
-    per_cu = std::max(1, per_cu - ctx->grid_headroom);
+    per_cu = std::max(1, per_cu - headroom);
     return (int)std::max<int64_t>(1, std::min<int64_t>(work, (int64_t)per_cu * ctx->cu_count));
 }
 
 // the context's second stream (a records job's general branch, the eq path's
 // staged copies), created on first use at the highest priority
-int ctx_fork(karma_ctx* ctx) {
+int ctx_fork(karma_ctx* ctx, bool own_stream) {
     if (!ctx->fork_a) {
         KARMA_HIP(hipEventCreateWithFlags(&ctx->fork_a, hipEventDisableTiming));
         KARMA_HIP(hipEventCreateWithFlags(&ctx->fork_b, hipEventDisableTiming));
     }
-    if (!ctx->fork_stream && !ctx->fork_use) {
+    if (!ctx->fork_stream && own_stream) {
         int lo = 0, hi = 0;
         KARMA_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
         KARMA_HIP(hipStreamCreateWithPriority(&ctx->fork_stream, hipStreamNonBlocking, hi));

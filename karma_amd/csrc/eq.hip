@@ -482,7 +482,7 @@ int graph_eq_run(karma_ctx* ctx, const int64_t* cls_off, const uint32_t* members
         KARMA_TRY(ctx_fork(ctx));
         for (int i = 0; i < 4; ++i)
             if (!ev[i]) KARMA_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-        xs = ctx->fork_use ? ctx->fork_use : ctx->fork_stream;
+        xs = ctx->fork_stream;
         KARMA_TRY(d_off.alloc(ctx, C + 1));
         KARMA_TRY(d_cnt.alloc(ctx, std::max<int64_t>(C, 1)));
         KARMA_TRY(d_mem.alloc(ctx, std::max<int64_t>(n_mem, 1)));
@@ -568,9 +568,8 @@ int graph_eq_run(karma_ctx* ctx, const int64_t* cls_off, const uint32_t* members
         if (compact) {
             if (C) {
                 KARMA_HIP(hipMemcpyAsync(d_c32.ptr, cq.counts32, C * 4, hipMemcpyHostToDevice, xs));
-                ctx->stream = xs;
+                StreamScope on_xs(ctx, xs);
                 KARMA_LAUNCH(ctx, "eq_widen", widen_counts_kernel, grid_of(C, 256), 256, 0, d_c32.ptr, C, d_cnt.ptr);
-                ctx->stream = ms;
             }
         } else if (C) {
             KARMA_HIP(hipMemcpyAsync(d_cnt.ptr, counts, C * 8, hipMemcpyHostToDevice, xs));
@@ -578,12 +577,11 @@ int graph_eq_run(karma_ctx* ctx, const int64_t* cls_off, const uint32_t* members
         KARMA_HIP(hipEventRecord(ev[3], xs));
     }
     {
-        ctx->stream = xs;
+        StreamScope on_xs(ctx, xs);
         if (N) KARMA_HIP(hipMemsetAsync(p->totals.ptr, 0, N * 8, xs));
         if (n_mem || compact)  // (compact: also checks the sizes' sum against n_mem)
             KARMA_LAUNCH(ctx, "eq_totals", eq_totals_kernel, grid_of(n_mem, kEqT), kEqT, 0, in, n_mem,
                          (unsigned long long*)p->totals.ptr, bad);
-        ctx->stream = ms;
         if (!is_device) KARMA_HIP(hipEventRecord(ev[0], xs));  // totals done (ev[0] reused)
     }
     if (P) {

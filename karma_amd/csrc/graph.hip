@@ -601,10 +601,8 @@ struct karma_graph_job {
     }
 };
 
-extern "C" {
-
-int karma_graph_records_begin(karma_ctx* ctx, const uint32_t* records, int64_t A, int64_t N, int flags, int is_device,
-                              karma_graph_job** out) {
+int karma::graph_records_begin(karma_ctx* ctx, const uint32_t* records, int64_t A, int64_t N, int flags, int is_device,
+                               const SetsOpts& opts, karma_graph_job** out) {
     KARMA_TRY(ctx_begin(ctx));
     KARMA_CHECK(out && (records || A == 0) && A >= 0, KARMA_ERR_ARG, "karma_graph_records: bad arguments");
     KARMA_CHECK(A < (int64_t(1) << 40), KARMA_ERR_ARG, "too many records");
@@ -633,7 +631,8 @@ int karma_graph_records_begin(karma_ctx* ctx, const uint32_t* records, int64_t A
         job->ownw.swap(ownw);
         RecIn in;
         in.fw = w;
-        rc = N > sets_max_contigs() ? records_to_pairs_sets(ctx, in, A, N, p) : sets_begin(ctx, in, A, N, &job->sets);
+        rc = N > sets_max_contigs() ? records_to_pairs_sets(ctx, in, A, N, p)
+                                    : sets_begin(ctx, in, A, N, opts, &job->sets);
         if (rc) {
             delete job;
             return rc;
@@ -675,7 +674,7 @@ int karma_graph_records_begin(karma_ctx* ctx, const uint32_t* records, int64_t A
     if (N > sets_max_contigs()) {  // wide path: runs to completion here
         rc = records_to_pairs_sets(ctx, in, A, N, p);
     } else {
-        rc = sets_begin(ctx, in, A, N, &job->sets);
+        rc = sets_begin(ctx, in, A, N, opts, &job->sets);
     }
     if (rc) {
         delete job;
@@ -683,6 +682,13 @@ int karma_graph_records_begin(karma_ctx* ctx, const uint32_t* records, int64_t A
     }
     *out = job;
     return KARMA_OK;
+}
+
+extern "C" {
+
+int karma_graph_records_begin(karma_ctx* ctx, const uint32_t* records, int64_t A, int64_t N, int flags, int is_device,
+                              karma_graph_job** out) {
+    return graph_records_begin(ctx, records, A, N, flags, is_device, SetsOpts{}, out);
 }
 
 int karma_graph_records_end(karma_graph_job* job, karma_pairs** out) {

@@ -2814,18 +2814,28 @@ int64_t chunk_records(const karma_ctx* ctx, int64_t A) {
     return ceil_div(A, kCChunk) < 4 * slots ? kCChunk / 2 : kCChunk;
 }
 // KARMA_MARK_AT in the environment wins; else the caller's choice
-// (ctx->mark_pos, the native step's deferred batches), else the default
-int mark_at(const karma_ctx* ctx) {
+// (SetsOpts::mark, the native step's deferred batches), else the default
+int mark_at(int asked) {
     static const int env = [] {
         const char* e = std::getenv("KARMA_MARK_AT");
         return e ? std::atoi(e) : -1;
     }();
-    return env >= 0 ? env : ctx->mark_pos >= 0 ? ctx->mark_pos : KARMA_MARK_AT;
+    return env >= 0 ? env : asked >= 0 ? asked : KARMA_MARK_AT;
+}
+// a run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+int pick(bool b, F f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
 }
 struct SetsJob {
     karma_ctx* ctx = nullptr;
     RecIn rec;
     int64_t A = 0, N = 0;
+    // The caller's options apply to setup() and the first launch only
+    // (begin_job puts the defaults back after it): a rerun from finish() forks
+    // onto the context's own fork stream and marks at the default position,
+    // whatever the job's caller chose; the control block taken is in cb / ext.
+    SetsOpts opts;
     Geo g{};
     int B = 0;
     int64_t n_chunks = 0;
@@ -2915,15 +2925,15 @@ int SetsJob::setup() {
     // one allocation (and one memset per attempt) for the control block and
     // the per-partition-block item counts behind it
     const int64_t cw_total = ctrl_words + 2 * n_pblk + B;
-    // a deferred job may take the caller's zeroed block (ctx->job_ctrl)
-    ext = deferred && ctx->job_ctrl && ctx->job_ctrl_words >= cw_total;
+    // a deferred job may take the caller's zeroed block (SetsOpts::ctrl)
+    ext = deferred && opts.ctrl && opts.ctrl_words >= cw_total;
     static const bool debug_ctrl = std::getenv("KARMA_DEBUG_CTRL") != nullptr;
     if (debug_ctrl)
         std::fprintf(stderr, "[karma] records job: deferred %d, caller block %p (%lld words), needs %lld: %s\n",
-                     (int)deferred, (void*)ctx->job_ctrl, (long long)ctx->job_ctrl_words, (long long)cw_total,
+                     (int)deferred, (void*)opts.ctrl, (long long)opts.ctrl_words, (long long)cw_total,
                      ext ? "caller's" : "own");
     if (ext) {
-        cb = ctx->job_ctrl;
+        cb = opts.ctrl;
     } else {
         KARMA_TRY(ctrl.alloc(ctx, cw_total));
         cb = ctrl.ptr;
@@ -3017,11 +3027,23 @@ int SetsJob::launch() {
     const bool probe = A > 0 && !relabeled && !fresh_ext;
     if (!probe && !fresh_ext) KARMA_HIP(hipMemsetAsync(cb, 0, (ctrl_words + 2 * n_pblk + B) * 8, ctx->stream));
     if (append) KARMA_HIP(hipMemsetAsync(blk_hist.ptr, 0, n_pblk * g.Bc * 4, ctx->stream));
-    if (mark_at(ctx) == 3 && attempt == 0 && !relabeled) {  // side-stream work may start beside classify
+    // where side-stream work (the k-mer profile) may start: 5 = after the final
+    // kernel, beside the control-block readback (default; 0.283 against 0.291
+    // ms for the 8-rank strong preview, equal on one GPU, profiles/r03/measurements.md (ab_mark5)),
+    // 0 = after the whole pipeline, 1 = after classify, 2 = after the code
+    // partition, 3 = at once (beside classify), 4 = after the code reduce.
+    // Measured: 1 slows the code partition 0.19 -> 0.5 ms (1.46 vs 1.37 ms/step);
+    // 2 stretches the profile to 0.60 ms beside the reduce (1.43 vs 1.35);
+    // 3 stretches classify 0.54 -> 0.74 ms (1.35 vs 1.25): HBM is already full
+    const int mark_here = mark_at(opts.mark);
+    auto mark = [&](int at) -> int {
+        if (mark_here != at || attempt != 0) return KARMA_OK;
         if (!ctx->mark_ev) KARMA_HIP(hipEventCreateWithFlags(&ctx->mark_ev, hipEventDisableTiming));
         KARMA_HIP(hipEventRecord(ctx->mark_ev, ctx->stream));
         ctx->mark_set = true;
-    }
+        return KARMA_OK;
+    };
+    if (!relabeled) KARMA_TRY(mark(3));  // side-stream work may start beside classify
     if (A > 0) {
         ClassArgs C{rec.pr,    A,         (uint32_t)N,   g.Bc > 0,     codes.ptr, n_codes.ptr,
                     n_gen.ptr, blk_items, lpb, big_list.ptr, counters, flags,
@@ -3035,38 +3057,20 @@ int SetsJob::launch() {
             C.c0 = c_from;
             const int64_t cg = ceil_div(c_to - c_from, kCW / 64);
             if (cg <= 0) return KARMA_OK;
-            if (rec.flagged()) {  // flagged records (4 bytes each)
-                if (bin && relabeled)
-                    KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<false, true, true, true, true>), cg, kCW, 0, C,
-                                 Bn);
-                else if (bin)
-                    KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<false, true, false, true, true>), cg, kCW, 0,
-                                 C, Bn);
-                else if (append && relabeled)
-                    KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<true, true, true, false, true>), cg, kCW, 0,
-                                 C, Bn);
-                else if (append)
-                    KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<true, true, false, false, true>), cg, kCW, 0,
-                                 C, Bn);
-                else if (relabeled)
-                    KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<false, true, true, false, true>), cg, kCW, 0,
-                                 C, Bn);
-                else
-                    KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<false, true, false, false, true>), cg, kCW, 0,
-                                 C, Bn);
-            } else if (bin && relabeled)
-                KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<false, true, true, true>), cg, kCW, 0, C, Bn);
-            else if (bin)
-                KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<false, true, false, true>), cg, kCW, 0, C, Bn);
-            else if (append && relabeled)
-                KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<true, true, true>), cg, kCW, 0, C, Bn);
-            else if (append)
-                KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<true, true>), cg, kCW, 0, C, Bn);
-            else if (relabeled)
-                KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<false, true, true>), cg, kCW, 0, C, Bn);
-            else
-                KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<false, true>), cg, kCW, 0, C, Bn);
-            return KARMA_OK;
+            // classify2_kernel<HIST (append), COMPACT, REMAP (relabelled), BIN, FLAG (flagged records)>
+            return pick(rec.flagged(), [&](auto fl) -> int {
+                auto go = [&](auto ap, auto bn) -> int {
+                    return pick(relabeled, [&](auto rl) -> int {
+                        KARMA_LAUNCH(ctx, "graph_classify",
+                                     (classify2_kernel<decltype(ap)::value, true, decltype(rl)::value,
+                                                       decltype(bn)::value, decltype(fl)::value>),
+                                     cg, kCW, 0, C, Bn);
+                        return KARMA_OK;
+                    });
+                };
+                return bin ? go(std::false_type{}, std::true_type{})
+                           : append ? go(std::true_type{}, std::false_type{}) : go(std::false_type{}, std::false_type{});
+            });
         };
         if (probe) {
             // a probe of the reads decides: when many span more than 4 contig
@@ -3080,21 +3084,6 @@ int SetsJob::launch() {
         }
         KARMA_TRY(classify(0, n_chunks));
     }
-    // where side-stream work (the k-mer profile) may start: 5 = after the final
-    // kernel, beside the control-block readback (default; 0.283 against 0.291
-    // ms for the 8-rank strong preview, equal on one GPU, profiles/r03/measurements.md (ab_mark5)),
-    // 0 = after the whole pipeline, 1 = after classify, 2 = after the code
-    // partition, 3 = at once (beside classify), 4 = after the code reduce.
-    // Measured: 1 slows the code partition 0.19 -> 0.5 ms (1.46 vs 1.37 ms/step);
-    // 2 stretches the profile to 0.60 ms beside the reduce (1.43 vs 1.35);
-    // 3 stretches classify 0.54 -> 0.74 ms (1.35 vs 1.25): HBM is already full
-    auto mark = [&](int at) -> int {
-        if (mark_at(ctx) != at || attempt != 0) return KARMA_OK;
-        if (!ctx->mark_ev) KARMA_HIP(hipEventCreateWithFlags(&ctx->mark_ev, hipEventDisableTiming));
-        KARMA_HIP(hipEventRecord(ctx->mark_ev, ctx->stream));
-        ctx->mark_set = true;
-        return KARMA_OK;
-    };
     KARMA_TRY(mark(1));
     if (A == 0) {
         KARMA_HIP(hipMemsetAsync(n_codes.ptr, 0, n_chunks * 4, ctx->stream));
@@ -3106,20 +3095,20 @@ int SetsJob::launch() {
     // Two independent branches after classify, joined by the final kernel:
     // general reads -> pair lists -> pair partition -> pair reduce, and the
     // code partition -> code reduce.  The first (three short kernels) runs on
-    // the context's fork stream beside the second.
+    // a fork stream (the caller's idle one, else the context's own) beside the second.
     hipStream_t const main_stream = ctx->stream;
     // (not while every launch is timed: the per-kernel pass wants each kernel
     // alone on the chip)
-    const bool fork = fork_on() && !ctx->no_fork && !(ctx->timing && ctx->timing_only.empty());
-    hipStream_t fork_s = nullptr;  // set by ctx_fork: ctx->fork_use or ctx->fork_stream
+    const bool fork = fork_on() && !opts.single_stream && !(ctx->timing && ctx->timing_only.empty());
+    hipStream_t fork_s = main_stream;
     if (fork) {
-        KARMA_TRY(ctx_fork(ctx));
-        fork_s = ctx->fork_use ? ctx->fork_use : ctx->fork_stream;
+        KARMA_TRY(ctx_fork(ctx, !opts.fork));
+        fork_s = opts.fork ? opts.fork : ctx->fork_stream;
         KARMA_HIP(hipEventRecord(ctx->fork_a, main_stream));
         KARMA_HIP(hipStreamWaitEvent(fork_s, ctx->fork_a, 0));
-        ctx->stream = fork_s;
     }
-    int rc_pair = [&]() -> int {
+    {
+        StreamScope on_fork(ctx, fork_s);
         KARMA_LAUNCH(ctx, "graph_general", general_kernel, general_grid(ctx, n_chunks), kGW, 0, rec, A, (uint32_t)N,
                      codes.ptr, n_gen.ptr, n_chunks, plist.ptr, pcap, n_pl.ptr, blk_items + n_pblk, lpb, flags,
                      relabeled ? (const uint32_t*)remap_map.ptr : nullptr, (const unsigned*)(counters + 3), chunk);
@@ -3132,10 +3121,7 @@ int SetsJob::launch() {
         KARMA_LAUNCH(ctx, "graph_pair_reduce", pair_reduce_kernel, nsl, kRT, 0, pent.ptr, pdir, n_pg, g.bw, g.bbits,
                      g.dbits, B, part_b.ptr, part_k.ptr, part_c.ptr, part_n.ptr, ovf);
         if (fork) KARMA_HIP(hipEventRecord(ctx->fork_b, fork_s));
-        return KARMA_OK;
-    }();
-    ctx->stream = main_stream;
-    KARMA_TRY(rc_pair);
+    }
     if (bin) {
         KARMA_LAUNCH(ctx, "graph_code_reduce", code_seg_reduce_kernel, (int64_t)g.Bc * n_cg, kCRT, 0, bsegs.ptr,
                      reinterpret_cast<const uint4*>(bhdr.ptr), bdir.ptr, n_chunks, seg_cap, dir_cap, g.bwc, n_cg,
@@ -3342,7 +3328,9 @@ int SetsJob::finish(karma_pairs* out) {
 
 int64_t sets_max_contigs() { return kMaxCompactN; }
 
-int sets_begin(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, SetsJob** job) {
+// deferred: no control-block readback (sets_begin_deferred)
+static int begin_job(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, const SetsOpts& opts, bool deferred,
+                     SetsJob** job) {
     KARMA_CHECK(N <= kMaxCompactN, KARMA_ERR_ARG, "sets_begin: n_contigs above the compact path");
     KARMA_CHECK(!ctx->job_open, KARMA_ERR_STATE, "a split graph call is already open on this context");
     std::unique_ptr<SetsJob> j(new SetsJob());
@@ -3350,6 +3338,8 @@ int sets_begin(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, SetsJob** job) {
     j->rec = rec;
     j->A = A;
     j->N = N;
+    j->opts = opts;
+    j->deferred = deferred;
     if (!ctx->split_bounds.empty() && (int)ctx->split_bounds.size() <= kMaxSplit) j->split_b = ctx->split_bounds;
     ctx->split_bounds.clear();  // one job
     KARMA_TRY(j->setup());
@@ -3358,9 +3348,14 @@ int sets_begin(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, SetsJob** job) {
         ctx->mark_set = false;
         return rc;
     }
+    j->opts = SetsOpts{};  // the first launch is out: a rerun takes the default schedule (see SetsJob::opts)
     ctx->job_open = true;
     *job = j.release();
     return KARMA_OK;
+}
+
+int sets_begin(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, const SetsOpts& opts, SetsJob** job) {
+    return begin_job(ctx, rec, A, N, opts, false, job);
 }
 
 int sets_end(SetsJob* job, karma_pairs* out) {
@@ -3378,23 +3373,10 @@ void sets_free(SetsJob* job) {
     delete job;
 }
 
-int sets_begin_deferred(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, SetsJob** job, SetsDeferred* v) {
-    KARMA_CHECK(N <= kMaxCompactN, KARMA_ERR_ARG, "sets_begin: n_contigs above the compact path");
-    KARMA_CHECK(!ctx->job_open, KARMA_ERR_STATE, "a split graph call is already open on this context");
-    std::unique_ptr<SetsJob> j(new SetsJob());
-    j->ctx = ctx;
-    j->rec = rec;
-    j->A = A;
-    j->N = N;
-    j->deferred = true;
-    if (!ctx->split_bounds.empty() && (int)ctx->split_bounds.size() <= kMaxSplit) j->split_b = ctx->split_bounds;
-    ctx->split_bounds.clear();  // one job
-    KARMA_TRY(j->setup());
-    const int rc = j->launch();
-    if (rc) {
-        ctx->mark_set = false;
-        return rc;
-    }
+int sets_begin_deferred(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, const SetsOpts& opts, SetsJob** job,
+                        SetsDeferred* v) {
+    KARMA_TRY(begin_job(ctx, rec, A, N, opts, true, job));
+    const SetsJob* j = *job;
     v->keys = j->slot_k.ptr;
     v->counts = j->slot_c.ptr;
     v->cap = (int64_t)j->B * kSlotCap;
@@ -3408,8 +3390,6 @@ int sets_begin_deferred(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, SetsJob
     v->ovf = j->ovf;
     v->ctrl = j->ext ? j->cb : nullptr;
     v->ctrl_need = j->ctrl_words + 2 * j->n_pblk + j->B;
-    ctx->job_open = true;
-    *job = j.release();
     return KARMA_OK;
 }
 
@@ -3423,7 +3403,7 @@ void sets_release(SetsJob* job) {
 int records_to_pairs_sets(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, karma_pairs* out) {
     if (N > kMaxCompactN) return records_to_pairs_wide(ctx, rec, A, N, out);
     SetsJob* job = nullptr;
-    KARMA_TRY(sets_begin(ctx, rec, A, N, &job));
+    KARMA_TRY(sets_begin(ctx, rec, A, N, SetsOpts{}, &job));
     return sets_end(job, out);
 }
 

@@ -86,11 +86,9 @@ struct karma_ctx {
     size_t job_pinned_bytes = 0;
     bool job_open = false;
     hipEvent_t side_ev = nullptr;  // main -> side stream ordering (karma_kmer_profile_side)
-    int grid_headroom = 0;         // blocks per CU resident_grid leaves free (a side-stream launch)
-    int side_headroom = 0;         // grid_headroom of karma_kmer_profile_side (karma_ctx_set_side_headroom)
-    hipEvent_t mark_ev = nullptr;  // recorded by an open graph job after its classify kernel
+    int side_headroom = 0;         // blocks per CU karma_kmer_profile_side leaves free (karma_ctx_set_side_headroom)
+    hipEvent_t mark_ev = nullptr;  // recorded by an open graph job at its mark position (SetsJob::launch)
     bool mark_set = false;
-    int mark_pos = -1;  // where an open graph job records mark_ev (SetsJob::launch); -1: the default
     int64_t* fin_pinned = nullptr;  // M of an in-flight karma_kmer_plan_finalize_async
     // mapped, coherent pinned host memory that kernels read and write directly
     // (one-launch consumers of small views: no copy launches)
@@ -105,39 +103,41 @@ struct karma_ctx {
     std::map<std::pair<const void*, std::pair<int, size_t>>, int> occupancy;
     // a records graph job's second branch (general reads' pairs: general,
     // pair partition, pair reduce) runs here beside the code branch, forked
-    // after classify and joined before the final kernel (SetsJob::launch)
+    // after classify and joined before the final kernel (SetsJob::launch),
+    // unless the job's caller brings a stream of its own (SetsOpts::fork)
     hipStream_t fork_stream = nullptr;
     hipEvent_t fork_a = nullptr, fork_b = nullptr;
     hipEvent_t xfer_ev[4] = {};  // the eq path's staged host->device copies on fork_stream
-    bool no_fork = false;        // the next records job keeps its general branch on its own stream
-    // an idle stream of the caller's to fork onto instead of fork_stream (a
-    // step's spare main stream): every stream the process creates takes one of
-    // its 4 hardware queues in turn, and a 6th stream shares the 2nd's -- a
-    // records job's main stream (config 3: 1.52 against 1.2 ms per step)
-    hipStream_t fork_use = nullptr;
     int64_t eq_pair_cap = 0;     // the eq path's previous pair total (its speculative scratch size)
-    // a zeroed control block the next deferred records job may use instead of
-    // its own (a native step's, kept zero by the step's status kernel): no
-    // clearing launch ahead of classify, no relabel probe (classify votes)
-    int64_t* job_ctrl = nullptr;
-    int64_t job_ctrl_words = 0;
-    // the next k-mer plan may take this zeroed block for its presence bitmap
-    // and exception counter (no clearing memset); its column table kernel
-    // clears it again (karma_step, per side stream)
-    uint32_t* plan_zeroed = nullptr;
-    int64_t plan_zeroed_words = 0;
 };
 
 namespace karma {
+
+// Redirects the context's current stream (where KARMA_LAUNCH, the allocator and
+// the library's own calls enqueue) for a scope, and puts the previous one back
+// on every way out of it, early error returns included.
+struct StreamScope {
+    karma_ctx* const ctx;
+    hipStream_t const prev;
+    StreamScope(karma_ctx* c, hipStream_t s) : ctx(c), prev(c->stream) { ctx->stream = s; }
+    ~StreamScope() { ctx->stream = prev; }
+    StreamScope(const StreamScope&) = delete;  // (no assignment either: const members)
+};
 
 int ctx_alloc(karma_ctx* ctx, size_t bytes, void** out);
 void ctx_free(karma_ctx* ctx, void* p);
 int ctx_begin(karma_ctx* ctx);  // hipSetDevice
 // Grid of one round: blocks that fit on the device at once for this kernel,
 // block size and dynamic LDS (at least 1, at most `work` blocks).
-int resident_grid(karma_ctx* ctx, const void* kernel, int block, size_t lds, int64_t work);
+// headroom: blocks per CU left free for another stream's short kernels.
+int resident_grid(karma_ctx* ctx, const void* kernel, int block, size_t lds, int64_t work, int headroom = 0);
+// Creates the two fork events and (own_stream) ctx->fork_stream on first use.
+// A caller that forks onto a stream of its own asks for the events only: every
+// stream the process creates takes one of its 4 hardware queues in turn, and
+// a 6th stream shares the 2nd's -- a records job's main stream (config 3: 1.52
+// against 1.2 ms per step).
+int ctx_fork(karma_ctx* ctx, bool own_stream = true);
 // Pinned host scratch of >= bytes (valid until the next call on this ctx).
-int ctx_fork(karma_ctx* ctx);  // creates ctx->fork_stream and its two events on first use
 int ctx_pinned(karma_ctx* ctx, size_t bytes, void** out);
 // Mapped coherent pinned host memory that kernels read and write directly.
 // One region per context, allocated once and freed only with the context, cut
@@ -233,9 +233,18 @@ int reduce_sorted(karma_ctx* ctx, const uint64_t* keys, const uint32_t* perm, co
                   const uint64_t* fin, int64_t n, uint64_t* uk, int64_t* uc, uint64_t* uf, int64_t* n_out_dev);
 
 // k-mer plan internals for karma_step (kmer.hip)
+// A zeroed block of the caller's that a plan may take for its presence bitmap
+// and exception counter (no clearing memset); the plan's column table kernel
+// clears it again (karma_step keeps one per side stream).
+struct PlanOpts {
+    uint32_t* zeroed = nullptr;
+    int64_t zeroed_words = 0;
+};
+// karma_kmer_plan_create with options (the public call passes none)
+int kmer_plan_create(karma_ctx* ctx, karma_contigs* c, int kmode, const PlanOpts& opts, karma_kmer_plan** out);
 int64_t kmer_m_cap(const karma_kmer_plan* p);
 int kmer_finalize_device(karma_kmer_plan* p, int64_t* m_out, int64_t* m_host);
-int kmer_profile_device_m(karma_kmer_plan* p, double* out_dev, const int64_t* m_dev);
+int kmer_profile_device_m(karma_kmer_plan* p, double* out_dev, const int64_t* m_dev, int headroom);  // resident_grid's
 int kmer_set_m(karma_kmer_plan* p, int64_t M);
 // graph.hip: a pending edge stage's status words (see karma_edges_end), handed over
 const int64_t* edges_take_pending(karma_edges* e);
@@ -279,13 +288,24 @@ struct RecIn {
 };
 // set-partition records pipeline (graph_sets.hip)
 int records_to_pairs_sets(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, karma_pairs* out);
+// A records job's per-call options (the defaults: a public call's).
+struct SetsOpts {
+    hipStream_t fork = nullptr;  // the caller's idle stream for the general-read branch; null: ctx->fork_stream
+    bool single_stream = false;  // the general-read branch stays on the job's own stream
+    int mark = -1;  // where the job records ctx->mark_ev (SetsJob::launch); -1: the default
+    // a zeroed control block a deferred job may use instead of its own (a
+    // native step's, kept zero by the step's status kernel): no clearing
+    // launch ahead of classify, no relabel probe (classify votes)
+    int64_t* ctrl = nullptr;
+    int64_t ctrl_words = 0;
+};
 // The same in two halves: sets_begin enqueues every kernel up to the control
 // block readback and returns; sets_end synchronises and assembles the list.
 // Only for N <= sets_max_contigs() (the compact path); `rec` must stay valid
 // until sets_end.
 struct SetsJob;
 int64_t sets_max_contigs();
-int sets_begin(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, SetsJob** job);
+int sets_begin(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, const SetsOpts& opts, SetsJob** job);
 int sets_end(SetsJob* job, karma_pairs* out);  // frees the job
 void sets_free(SetsJob* job);
 // A records job launched without its control-block readback (karma_step's
@@ -302,10 +322,14 @@ struct SetsDeferred {
     const int* flags = nullptr;       // [0] unsorted, [1] contig range, [2] pair capacity, [3] partition check
     const unsigned* counters = nullptr;  // [0] big reads, [3] relabel vote
     const uint8_t* ovf = nullptr;     // per bucket: overflowed the LDS tables (generic path needed)
-    int64_t* ctrl = nullptr;          // the caller's control block when the job used it (ctx->job_ctrl), else null
-    int64_t ctrl_need = 0;            // words of control block the job needed (a larger ctx->job_ctrl next time)
+    int64_t* ctrl = nullptr;          // the caller's control block when the job used it (SetsOpts::ctrl), else null
+    int64_t ctrl_need = 0;            // words of control block the job needed (a larger SetsOpts::ctrl next time)
 };
-int sets_begin_deferred(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, SetsJob** job, SetsDeferred* view);
+int sets_begin_deferred(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, const SetsOpts& opts, SetsJob** job,
+                        SetsDeferred* view);
+// graph.hip: karma_graph_records_begin with options (the public call passes the defaults)
+int graph_records_begin(karma_ctx* ctx, const uint32_t* records, int64_t A, int64_t N, int flags, int is_device,
+                        const SetsOpts& opts, karma_graph_job** out);
 // Frees a deferred job's buffers to the allocator (stream-ordered; no wait).
 void sets_release(SetsJob* job);
 }  // namespace karma

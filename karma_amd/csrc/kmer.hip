@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 
 #include "karma_internal.h"
 
@@ -54,7 +55,7 @@ struct karma_kmer_plan {
     DevArray<uint32_t> presence;
     // the bitmap (nwords, padded to even) then the exception k-mer counter (2
     // words): inside `presence`, or the caller's zeroed block (bits_ext:
-    // ctx->plan_zeroed, karma_step's; the column table kernel clears it again)
+    // PlanOpts::zeroed, karma_step's; the column table kernel clears it again)
     uint32_t* bits = nullptr;
     bool bits_ext = false;
     DevArray<uint64_t> exc_keys;  // sorted unique
@@ -1063,14 +1064,17 @@ int karma_contigs_info(karma_contigs* c, int64_t* n, int64_t* total, int64_t* ex
     return KARMA_OK;
 }
 
-int karma_kmer_plan_create(karma_ctx* ctx, karma_contigs* c, int kmode, karma_kmer_plan** out) {
+}  // extern "C"
+
+int karma::kmer_plan_create(karma_ctx* ctx, karma_contigs* c, int kmode, const PlanOpts& opts, karma_kmer_plan** out) {
     KARMA_TRY(ctx_begin(ctx));
     KARMA_CHECK(c && out, KARMA_ERR_ARG, "karma_kmer_plan_create: bad arguments");
     int kmin, kmax;
     uint32_t S;
     bool with_len;
     KARMA_TRY(kmer_shape(kmode, &kmin, &kmax, &S, &with_len));
-    auto* p = new karma_kmer_plan();
+    // held until the function succeeds, so every early return frees it
+    std::unique_ptr<karma_kmer_plan> p(new karma_kmer_plan());
     p->ctx = ctx;
     p->store = c;
     p->kmode = kmode;
@@ -1087,13 +1091,11 @@ int karma_kmer_plan_create(karma_ctx* ctx, karma_contigs* c, int kmode, karma_km
     const int64_t nrow = c->n ? c->n : 1;
     // a caller's zeroed bitmap block (karma_step): no clearing memset; the
     // row totals need none (every profile launch writes or clears its rows)
-    p->bits_ext = ctx->plan_zeroed && ctx->plan_zeroed_words >= pw + 2;
+    p->bits_ext = opts.zeroed && opts.zeroed_words >= pw + 2;
     if ((rc = p->presence.alloc(ctx, (p->bits_ext ? 0 : pw + 2) + 2 * nrow)) || (rc = p->err.alloc(ctx, 1)) ||
-        (rc = exc_buf.alloc(ctx, exc_cap))) {
-        delete p;
+        (rc = exc_buf.alloc(ctx, exc_cap)))
         return rc;
-    }
-    p->bits = p->bits_ext ? ctx->plan_zeroed : p->presence.ptr;
+    p->bits = p->bits_ext ? opts.zeroed : p->presence.ptr;
     if (!p->bits_ext) KARMA_HIP(hipMemsetAsync(p->presence.ptr, 0, (pw + 2 + 2 * nrow) * 4, ctx->stream));
     struct {
         unsigned long long* ptr;
@@ -1130,12 +1132,15 @@ int karma_kmer_plan_create(karma_ctx* ctx, karma_contigs* c, int kmode, karma_km
     }
     KARMA_CHECK((int64_t)ninst <= exc_cap, KARMA_ERR_STATE, "exception k-mer buffer overflow (%llu > %lld)", ninst,
                 (long long)exc_cap);
-    if (ninst && (rc = sort_unique_keys(ctx, exc_buf.ptr, (int64_t)ninst, p->exc_keys, &p->n_exc))) {
-        delete p;
-        return rc;
-    }
-    *out = p;
+    if (ninst && (rc = sort_unique_keys(ctx, exc_buf.ptr, (int64_t)ninst, p->exc_keys, &p->n_exc))) return rc;
+    *out = p.release();
     return KARMA_OK;
+}
+
+extern "C" {
+
+int karma_kmer_plan_create(karma_ctx* ctx, karma_contigs* c, int kmode, karma_kmer_plan** out) {
+    return kmer_plan_create(ctx, c, kmode, PlanOpts{}, out);
 }
 
 int karma_kmer_plan_destroy(karma_kmer_plan* p) {
@@ -1232,7 +1237,7 @@ int karma_kmer_plan_finalize_async(karma_kmer_plan* p) {
 }  // extern "C"
 
 static int profile_rows(karma_kmer_plan* p, int64_t lo, int64_t hi, double* out, int64_t ld, int out_is_device,
-                        const int64_t* m_dev);
+                        const int64_t* m_dev, int headroom = 0);
 
 namespace karma {
 // The column table without M's readback (karma_step's deferred steps): M is
@@ -1257,8 +1262,8 @@ int kmer_finalize_device(karma_kmer_plan* p, int64_t* m_out, int64_t* m_host) {
     return KARMA_OK;
 }
 
-int kmer_profile_device_m(karma_kmer_plan* p, double* out_dev, const int64_t* m_dev) {
-    return profile_rows(p, 0, p->store->n, out_dev, 0, 1, m_dev);
+int kmer_profile_device_m(karma_kmer_plan* p, double* out_dev, const int64_t* m_dev, int headroom) {
+    return profile_rows(p, 0, p->store->n, out_dev, 0, 1, m_dev, headroom);
 }
 
 // the column keys of a plan finalized on the device, once M is known
@@ -1316,8 +1321,9 @@ int karma_kmer_row_totals(karma_kmer_plan* p, int64_t* dst) {
 // m_dev: M is read by the kernels from the column table's count on the device
 // (karma_step's path: no host wait for it); the launch is sized for
 // kmer_m_cap(p) >= M and rows are written dense (ld = M).
+// headroom: blocks per CU the wave kernel's one-round grid leaves free (resident_grid).
 static int profile_rows(karma_kmer_plan* p, int64_t lo, int64_t hi, double* out, int64_t ld, int out_is_device,
-                        const int64_t* m_dev) {
+                        const int64_t* m_dev, int headroom) {
     KARMA_CHECK(p && (p->M >= 0 || m_dev), KARMA_ERR_STATE, "karma_kmer_profile before finalize");
     karma_ctx* ctx = p->ctx;
     karma_contigs* c = p->store;
@@ -1371,7 +1377,7 @@ static int profile_rows(karma_kmer_plan* p, int64_t lo, int64_t hi, double* out,
 #define KARMA_WAVE_LAUNCH(P56, C16)                                                                              \
     do {                                                                                                         \
         const int g_ = resident_grid(ctx, reinterpret_cast<const void*>(&profile_wave_kernel<P56, C16>), kPBlock, \
-                                     lds, ceil_div(n, kPBlock / 64));                                            \
+                                     lds, ceil_div(n, kPBlock / 64), headroom);                                  \
         KARMA_LAUNCH(ctx, "kmer_profile", (profile_wave_kernel<P56, C16>), g_, kPBlock, lds, c->packed.ptr,      \
                      c->mask.ptr, c->has_exc.ptr, woff, off, c->raw, keylen, n, k, with_len,                     \
                      p->col_of_ord.ptr, p->exc_keys.ptr, p->n_exc, p->col_of_exc.ptr, M, dst, ld, err,       \
@@ -1440,15 +1446,11 @@ int karma_kmer_profile_side(karma_kmer_plan* p, double* out_dev, int64_t ld, voi
         KARMA_HIP(hipEventRecord(ctx->side_ev, ctx->stream));  // after everything enqueued on the main stream
         KARMA_HIP(hipStreamWaitEvent(s, ctx->side_ev, 0));
     }
-    hipStream_t main_stream = ctx->stream;
-    ctx->stream = s;  // launches and timing events go to the side stream
-    // its one-round grid leaves a block slot per CU, so the main stream's
-    // short kernels find room beside it instead of queueing behind it
-    ctx->grid_headroom = ctx->side_headroom;
-    const int rc = karma_kmer_profile(p, out_dev, ld, 1);
-    ctx->grid_headroom = 0;
-    ctx->stream = main_stream;
-    return rc;
+    StreamScope on_side(ctx, s);  // launches and timing events go to the side stream
+    // its one-round grid leaves side_headroom block slots per CU, so the main
+    // stream's short kernels find room beside it instead of queueing behind it
+    KARMA_CHECK(p->store, KARMA_ERR_STATE, "karma_kmer_profile: null plan");
+    return profile_rows(p, 0, p->store->n, out_dev, ld, 1, nullptr, ctx->side_headroom);
 }
 
 int karma_ctx_set_side_headroom(karma_ctx* ctx, int blocks_per_cu) {

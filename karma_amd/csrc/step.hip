@@ -602,7 +602,7 @@ struct karma_step {
     // steps: identical shapes reuse them)
     DevArray<int64_t> m_ring;      // per ring entry: the step's column count, written by its column table
     // per side stream: the k-mer plan's presence bitmap block, zero between
-    // plans (ctx->plan_zeroed; the column table kernel clears it after use)
+    // plans (PlanOpts::zeroed; the column table kernel clears it after use)
     DevArray<uint32_t> plan_zero[2];
     struct Tail {
         DevArray<double> prof;         // the step's profile
@@ -878,23 +878,24 @@ int run_sync(karma_step* s, karma_contigs* store, const uint32_t* rec, int64_t A
         // column set's exchange and the column table beside them on the side
         // stream; the profile behind the graph's kernels on the side stream
         karma_graph_job* job = nullptr;
-        ctx->fork_use = s->alt_s;  // the general-read branch on the spare main stream (see karma_ctx::fork_use)
-        const int brc = karma_graph_records_begin(ctx, rec, A, s->n_glob, rfmt, 1, &job);
-        ctx->fork_use = nullptr;
-        KARMA_TRY(brc);
+        SetsOpts jo;
+        jo.fork = s->alt_s;  // the general-read branch on the spare main stream (see ctx_fork)
+        KARMA_TRY(graph_records_begin(ctx, rec, A, s->n_glob, rfmt, 1, jo, &job));
         int rc = KARMA_OK;
-        ctx->stream = s->side_s;
-        rc = karma_kmer_plan_create(ctx, store, s->kmode, &s->plan);
-        if (!rc && s->world > 1 && s->acgt_store != store) {
-            // may later steps skip the exception keys' exchange?  (every rank agrees)
-            int64_t exc = 0;
-            rc = karma_contigs_info(store, nullptr, nullptr, &exc, nullptr);
-            if (!rc) rc = karma_comm_allreduce_host(s->scomm ? s->scomm : s->comm, &exc, 1, KARMA_DT_I64, KARMA_OP_SUM);
-            if (!rc) s->acgt_store = exc == 0 ? store : nullptr;
+        {
+            StreamScope on_side(ctx, s->side_s);
+            rc = karma_kmer_plan_create(ctx, store, s->kmode, &s->plan);
+            if (!rc && s->world > 1 && s->acgt_store != store) {
+                // may later steps skip the exception keys' exchange?  (every rank agrees)
+                int64_t exc = 0;
+                rc = karma_contigs_info(store, nullptr, nullptr, &exc, nullptr);
+                if (!rc)
+                    rc = karma_comm_allreduce_host(s->scomm ? s->scomm : s->comm, &exc, 1, KARMA_DT_I64, KARMA_OP_SUM);
+                if (!rc) s->acgt_store = exc == 0 ? store : nullptr;
+            }
+            if (!rc && s->world > 1) rc = exchange_columns(s, s->plan, s->scomm ? s->scomm : s->comm);
+            if (!rc) rc = karma_kmer_plan_finalize_async(s->plan);
         }
-        if (!rc && s->world > 1) rc = exchange_columns(s, s->plan, s->scomm ? s->scomm : s->comm);
-        if (!rc) rc = karma_kmer_plan_finalize_async(s->plan);
-        ctx->stream = s->main_s;
         if (!rc) rc = karma_kmer_plan_finalize_wait(s->plan, &M);
         if (!rc) rc = ensure_prof(s, s->prof, (size_t)std::max<int64_t>(1, s->n_loc * M));
         if (!rc && s->n_loc * M) rc = karma_kmer_profile_side(s->plan, s->prof.ptr, M, s->side_s);
@@ -1124,7 +1125,7 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
             }
         }
     } fail{s, tl, seq};
-    ctx->stream = ms;
+    StreamScope on_main(ctx, ms);
     s->prof_seq = seq;
     s->prof_par = par;
     s->prof_M = -1;
@@ -1132,28 +1133,23 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
     // records job (main stream) up to its final kernel; no readback
     SetsJob* job = nullptr;
     SetsDeferred v;
+    SetsOpts jo;
     // the general-read branch: on the idle spare main stream with one main
     // stream; kept on the main stream with two (see side_alt_s)
-    ctx->no_fork = two && s->sides == 2;
-    ctx->fork_use = two ? nullptr : s->alt_s;
+    jo.single_stream = two && s->sides == 2;
+    jo.fork = two ? nullptr : s->alt_s;
     // where the side stream's profile may start (SetsJob::launch): with one main
     // stream, after the code partition -- the profile's writes then share HBM
     // with the LDS-bound code reduce and final kernel instead of the next
     // batch's classify (config 3: 1.15 against 1.20-1.22 ms per step,
     // profiles/r04/measurements.md (ab_mark3)); with two, after the final kernel
-    ctx->mark_pos = two ? kMarkTwo : flg ? kMarkOneFlagged : kMarkOne;
-    ctx->job_ctrl = s->own_ctrl ? tl.ctrl.ptr : nullptr;  // zero: the last status kernel of this tail cleared it
-    ctx->job_ctrl_words = s->own_ctrl ? (int64_t)tl.ctrl.n : 0;
+    jo.mark = two ? kMarkTwo : flg ? kMarkOneFlagged : kMarkOne;
+    jo.ctrl = s->own_ctrl ? tl.ctrl.ptr : nullptr;  // zero: the last status kernel of this tail cleared it
+    jo.ctrl_words = s->own_ctrl ? (int64_t)tl.ctrl.n : 0;
     RecIn rin;
     if (flg) rin.fw = rec;
     else rin.pr = reinterpret_cast<const uint2*>(rec);
-    const int jrc = sets_begin_deferred(ctx, rin, A, s->n_glob, &job, &v);
-    ctx->job_ctrl = nullptr;
-    ctx->job_ctrl_words = 0;
-    ctx->mark_pos = -1;
-    ctx->no_fork = false;
-    ctx->fork_use = nullptr;
-    KARMA_TRY(jrc);
+    KARMA_TRY(sets_begin_deferred(ctx, rin, A, s->n_glob, jo, &job, &v));
     std::unique_ptr<SetsJob, void (*)(SetsJob*)> jg(job, sets_release);
     if (v.ctrl) ++s->n_own;
     if (s->own_ctrl && !v.ctrl) {
@@ -1171,66 +1167,67 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
     // profile behind the graph's final kernel (sequential: all on the main
     // stream, every kernel alone on the chip -- the per-kernel timing pass)
     hipStream_t const side = sequential ? ms : (par && s->sides == 2 && !xs_on ? s->side_alt_s : s->side_s);
-    ctx->stream = side;
-    DevArray<uint32_t>& pz = s->plan_zero[side == s->side_alt_s ? 1 : 0];
-    if (!sequential) {
-        // 2,048 + 2 words: the bitmap of every k <= 8 and the exception counter
-        if (!pz.ptr) {
-            KARMA_TRY(pz.alloc(ctx, 2048 + 2));
-            KARMA_HIP(hipMemsetAsync(pz.ptr, 0, pz.n * 4, side));
-        }
-        ctx->plan_zeroed = pz.ptr;
-        ctx->plan_zeroed_words = (int64_t)pz.n;
-    }
-    karma_kmer_plan* plan = nullptr;
-    int rc = karma_kmer_plan_create(ctx, store, s->kmode, &plan);
-    ctx->plan_zeroed = nullptr;
-    ctx->plan_zeroed_words = 0;
-    if (!rc && s->world > 1) {
-        if (xs_on && s->one_comm) {
-            // the presence all-gather on the exchange stream (behind the previous
-            // batch's tail and a synchronous step's collectives), the column
-            // table back on the side stream behind it
-            rc = stream_after(&s->ev_pres, side, xs);
-            if (!rc && s->sync_set) {
-                rc = stream_after(&s->ev_sync, s->main_s, xs);
-                s->sync_set = false;
+    int rc = KARMA_OK;
+    {
+        StreamScope on_side(ctx, side);
+        DevArray<uint32_t>& pz = s->plan_zero[side == s->side_alt_s ? 1 : 0];
+        PlanOpts po;
+        if (!sequential) {
+            // 2,048 + 2 words: the bitmap of every k <= 8 and the exception counter
+            if (!pz.ptr) {
+                KARMA_TRY(pz.alloc(ctx, 2048 + 2));
+                KARMA_HIP(hipMemsetAsync(pz.ptr, 0, pz.n * 4, side));
             }
-            ctx->stream = xs;
-            if (!rc) rc = exchange_presence(s, plan, s->comm);
-            if (!rc) rc = stream_after(&s->ev_pres2, xs, side);
-            ctx->stream = side;
-        } else {
-            // sequential (one stream), or the side communicator on the side stream
-            rc = exchange_presence(s, plan, s->scomm ? s->scomm : s->comm);
+            po.zeroed = pz.ptr;
+            po.zeroed_words = (int64_t)pz.n;
         }
+        karma_kmer_plan* plan = nullptr;
+        rc = kmer_plan_create(ctx, store, s->kmode, po, &plan);
+        if (!rc && s->world > 1) {
+            if (xs_on && s->one_comm) {
+                // the presence all-gather on the exchange stream (behind the previous
+                // batch's tail and a synchronous step's collectives), the column
+                // table back on the side stream behind it
+                rc = stream_after(&s->ev_pres, side, xs);
+                if (!rc && s->sync_set) {
+                    rc = stream_after(&s->ev_sync, s->main_s, xs);
+                    s->sync_set = false;
+                }
+                {
+                    StreamScope on_xs(ctx, xs);
+                    if (!rc) rc = exchange_presence(s, plan, s->comm);
+                    if (!rc) rc = stream_after(&s->ev_pres2, xs, side);
+                }
+            } else {
+                // sequential (one stream), or the side communicator on the side stream
+                rc = exchange_presence(s, plan, s->scomm ? s->scomm : s->comm);
+            }
+        }
+        // M: into the device ring (the profile reads it) and the mapped ring (the
+        // host reads it once the step is done); nothing on the main streams waits for it
+        int64_t* const m_dev = s->m_ring.ptr + seq % kRing;
+        if (!rc) rc = kmer_finalize_device(plan, m_dev, s->mring_d + seq % kRing);
+        // (a failed plan's block was not cleared by a column table)
+        if (rc && !sequential && pz.ptr) (void)hipMemsetAsync(pz.ptr, 0, pz.n * 4, side);
+        if (!rc) rc = ensure_prof(s, tl.prof, (size_t)std::max<int64_t>(1, s->n_loc * kmer_m_cap(plan)));
+        if (!rc && ctx->mark_set && !sequential) {
+            if (counted_call("hipStreamWaitEvent")) ++t_hip_calls;
+            rc = hipStreamWaitEvent(side, ctx->mark_ev, 0) == hipSuccess ? KARMA_OK : KARMA_ERR_HIP;
+        }
+        if (!rc && s->n_loc) {
+            // KARMA_STEP_HEADROOM (A/B): profile blocks per CU left free for the
+            // main stream's kernels (one main stream only)
+            static const int headroom = getenv("KARMA_STEP_HEADROOM") ? atoi(getenv("KARMA_STEP_HEADROOM")) : 0;
+            rc = kmer_profile_device_m(plan, tl.prof.ptr, m_dev, two || sequential ? 0 : headroom);
+        }
+        if (!rc && !two && !sequential && s->join) {
+            if (!s->ev && hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) rc = KARMA_ERR_HIP;
+            if (counted_call("hipEventRecord")) ++t_hip_calls;
+            if (!rc) rc = hipEventRecord(s->ev, side) == hipSuccess ? KARMA_OK : KARMA_ERR_HIP;
+            s->ev_set = !rc;
+        }
+        if (plan) karma_kmer_plan_destroy(plan);  // its buffers return to the side stream's cache
     }
-    // M: into the device ring (the profile reads it) and the mapped ring (the
-    // host reads it once the step is done); nothing on the main streams waits for it
-    int64_t* const m_dev = s->m_ring.ptr + seq % kRing;
-    if (!rc) rc = kmer_finalize_device(plan, m_dev, s->mring_d + seq % kRing);
-    if (rc && !sequential && pz.ptr) (void)hipMemsetAsync(pz.ptr, 0, pz.n * 4, side);  // not cleared by a column table
-    if (!rc) rc = ensure_prof(s, tl.prof, (size_t)std::max<int64_t>(1, s->n_loc * kmer_m_cap(plan)));
-    if (!rc && ctx->mark_set && !sequential) {
-        if (counted_call("hipStreamWaitEvent")) ++t_hip_calls;
-        rc = hipStreamWaitEvent(side, ctx->mark_ev, 0) == hipSuccess ? KARMA_OK : KARMA_ERR_HIP;
-    }
-    if (!rc && s->n_loc) {
-        // KARMA_STEP_HEADROOM (A/B): profile blocks per CU left free for the
-        // main stream's kernels (one main stream only)
-        static const int headroom = getenv("KARMA_STEP_HEADROOM") ? atoi(getenv("KARMA_STEP_HEADROOM")) : 0;
-        ctx->grid_headroom = two || sequential ? 0 : headroom;
-        rc = kmer_profile_device_m(plan, tl.prof.ptr, m_dev);
-        ctx->grid_headroom = 0;
-    }
-    if (!rc && !two && !sequential && s->join) {
-        if (!s->ev && hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) rc = KARMA_ERR_HIP;
-        if (counted_call("hipEventRecord")) ++t_hip_calls;
-        if (!rc) rc = hipEventRecord(s->ev, side) == hipSuccess ? KARMA_OK : KARMA_ERR_HIP;
-        s->ev_set = !rc;
-    }
-    if (plan) karma_kmer_plan_destroy(plan);  // its buffers return to the side stream's cache
-    ctx->stream = ms;
     KARMA_TRY(rc);
     if (xs_on) {  // the tail on the exchange stream, behind this records job (and a synchronous step's collectives)
         KARMA_TRY(stream_after(&s->ev_rec, ms, xs));
@@ -1239,8 +1236,8 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
             KARMA_TRY(stream_after(&s->ev_sync, s->main_s, xs));
             s->sync_set = false;
         }
-        ctx->stream = xs;
     }
+    StreamScope on_tail(ctx, xs_on ? xs : ms);
     // main stream: the tail, sized on the device
     const uint64_t* lk = v.keys;
     const int64_t* lc = v.counts;
@@ -1325,7 +1322,6 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
         KARMA_HIP(hipEventRecord(s->ev_tail[par], xs));
         s->tail_set[par] = true;
         s->tail_last = par;
-        ctx->stream = ms;
     }
     fail.armed = false;
     s->pending.push_back({seq, store, rec, A, flg});
@@ -1402,11 +1398,8 @@ int karma_step_create(karma_ctx* ctx, karma_comm* comm, karma_comm* side_comm, i
     s->mring_d = reinterpret_cast<int64_t*>(static_cast<uint8_t*>(dm) + kRing * sizeof(StepStatus));
     KARMA_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->graves_h), kRing * 4 * 8, hipHostMallocDefault));
     {
-        hipStream_t prev = ctx->stream;
-        ctx->stream = s->main_s;
-        const int rc = s->m_ring.alloc(ctx, kRing);
-        ctx->stream = prev;
-        KARMA_TRY(rc);
+        StreamScope on_main(ctx, s->main_s);
+        KARMA_TRY(s->m_ring.alloc(ctx, kRing));
     }
     s->ring_h = static_cast<StepStatus*>(hm);
     s->ring_d = static_cast<StepStatus*>(dm);
@@ -1435,8 +1428,7 @@ int karma_step_run(karma_step* s, karma_contigs* store, const uint32_t* records,
     KARMA_CHECK(n_store == s->n_loc, KARMA_ERR_ARG, "karma_step_run: the store holds %lld contigs, the shard %lld",
                 (long long)n_store, (long long)s->n_loc);
     const auto t0 = std::chrono::steady_clock::now();
-    hipStream_t prev = ctx->stream;
-    ctx->stream = s->main_s;
+    StreamScope on_main(ctx, s->main_s);
     const bool keep = flags & KARMA_STEP_KEEP, seq = flags & KARMA_STEP_SEQUENTIAL;
     const bool flg = flags & KARMA_STEP_FLAGGED;
     // deferred: one process (no collective needs a host count), nothing read back
@@ -1462,7 +1454,6 @@ int karma_step_run(karma_step* s, karma_contigs* store, const uint32_t* records,
         rc = drain(s, true);  // earlier deferred steps complete and checked first
         if (!rc) rc = run_sync(s, store, records, n_records, flg, keep, seq, !(flags & KARMA_STEP_DEFER));
     }
-    ctx->stream = prev;
     s->run_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
     if (rc) return rc;
     if (info) {
@@ -1478,11 +1469,10 @@ int karma_step_sync(karma_step* s) {
     KARMA_CHECK(s, KARMA_ERR_ARG, "null step");
     karma_ctx* ctx = s->ctx;
     KARMA_TRY(ctx_begin(ctx));
-    hipStream_t prev = ctx->stream;
-    ctx->stream = s->main_s;
-    int rc = drain(s, true);
-    ctx->stream = prev;
-    KARMA_TRY(rc);
+    {
+        StreamScope on_main(ctx, s->main_s);
+        KARMA_TRY(drain(s, true));
+    }
     KARMA_HIP(hipStreamSynchronize(s->side_s));
     KARMA_HIP(hipStreamSynchronize(s->side_alt_s));
     KARMA_HIP(hipStreamSynchronize(s->alt_s));
@@ -1522,11 +1512,8 @@ int karma_step_profile(karma_step* s, double** dev, int64_t* rows, int64_t* M) {
 int karma_step_columns(karma_step* s, uint64_t* keys_host) {
     KARMA_CHECK(s && s->plan, KARMA_ERR_STATE, "karma_step_columns: no kept step");
     KARMA_TRY(ctx_begin(s->ctx));
-    hipStream_t prev = s->ctx->stream;
-    s->ctx->stream = s->main_s;
-    const int rc = karma_kmer_columns(s->plan, keys_host);
-    s->ctx->stream = prev;
-    return rc;
+    StreamScope on_main(s->ctx, s->main_s);
+    return karma_kmer_columns(s->plan, keys_host);
 }
 
 int karma_step_edges(karma_step* s, karma_edges** e) {
