@@ -244,7 +244,7 @@ struct PlanOpts {
 int kmer_plan_create(karma_ctx* ctx, karma_contigs* c, int kmode, const PlanOpts& opts, karma_kmer_plan** out);
 int64_t kmer_m_cap(const karma_kmer_plan* p);
 int kmer_finalize_device(karma_kmer_plan* p, int64_t* m_out, int64_t* m_host);
-int kmer_profile_device_m(karma_kmer_plan* p, double* out_dev, const int64_t* m_dev, int headroom);  // resident_grid's
+int kmer_profile_device_m(karma_kmer_plan* p, double* out_dev, const int64_t* m_dev);
 int kmer_set_m(karma_kmer_plan* p, int64_t M);
 // graph.hip: a pending edge stage's status words (see karma_edges_end), handed over
 const int64_t* edges_take_pending(karma_edges* e);

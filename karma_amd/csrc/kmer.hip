@@ -516,24 +516,16 @@ __global__ void __launch_bounds__(kColBlock) columns_kernel(const uint32_t* pres
 // profile_wave_kernel: one wave per contig (M <= kWaveMaxM); profile_kernel:
 // one block per contig (large M).
 constexpr int kWaveMaxM = 4096;
-#ifndef KARMA_PROF_C16
-#define KARMA_PROF_C16 1
-#endif
 typedef double d2 __attribute__((ext_vector_type(2)));
-#ifndef KARMA_ROW_AUX
-// cache policy of the profile's 16-byte row stores, as buffer stores (-1: global
-// stores, non-temporal per KARMA_PROF_NT).  18 = sc1 | nt: profile 0.361 -> 0.348 ms;
-// measured alongside: 2 (nt) 0.358, 3 (sc0 | nt) 0.357, 19 0.353, 16 (sc1) 0.355
-// with a slower step (1.30 vs 1.25 ms), 17 (sc0 | sc1) 0.354 with 1.28 ms
-#define KARMA_ROW_AUX 18
-#endif
-#ifndef KARMA_PROF_NT
-#define KARMA_PROF_NT 1  // profile rows written with non-temporal stores
-#endif
+// cache policy of the profile's 16-byte row stores, which are buffer stores.
+// 18 = sc1 | nt: profile 0.361 -> 0.348 ms; measured alongside: 2 (nt) 0.358,
+// 3 (sc0 | nt) 0.357, 19 0.353, 16 (sc1) 0.355 with a slower step (1.30 vs
+// 1.25 ms), 17 (sc0 | sc1) 0.354 with 1.28 ms
+constexpr int kRowAux = 18;
+// a row's other elements (an odd last column, the unvectorised path): non-temporal
 template <typename T>
 __device__ __forceinline__ void row_store(T v, T* p) {
-    if (KARMA_PROF_NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
+    __builtin_nontemporal_store(v, p);
 }
 
 template <bool P56, typename Add>
@@ -699,21 +691,16 @@ __device__ __forceinline__ void write_row_wave(double* __restrict__ row, uint32_
             d2 v;
             v.x = val(a);
             v.y = val(b);
-#if KARMA_ROW_AUX >= 0  // the row's 16-byte stores as buffer stores with this cache policy
-            {
-                typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-                const uint64_t u = (uint64_t)row;
-                const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-                    reinterpret_cast<void*>(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(u >> 32)) << 32) |
-                                            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u)),
-                    0, (int)(M * 8), 0x00020000);
-                const u32x4_t w = {(uint32_t)__double2loint(v.x), (uint32_t)__double2hiint(v.x),
-                                   (uint32_t)__double2loint(v.y), (uint32_t)__double2hiint(v.y)};
-                __builtin_amdgcn_raw_buffer_store_b128(w, rr, (int)(j * 16), 0, KARMA_ROW_AUX);
-            }
-#else
-            row_store(v, reinterpret_cast<d2*>(row) + j);
-#endif
+            // the row's 16-byte stores as buffer stores with the kRowAux cache policy
+            typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+            const uint64_t u = (uint64_t)row;
+            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+                reinterpret_cast<void*>(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(u >> 32)) << 32) |
+                                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u)),
+                0, (int)(M * 8), 0x00020000);
+            const u32x4_t w = {(uint32_t)__double2loint(v.x), (uint32_t)__double2hiint(v.x),
+                               (uint32_t)__double2loint(v.y), (uint32_t)__double2hiint(v.y)};
+            __builtin_amdgcn_raw_buffer_store_b128(w, rr, (int)(j * 16), 0, kRowAux);
         }
         if ((M & 1) && lane == 0) {
             const uint32_t a = C16 ? counts[M >> 1] & 0xFFFFu : counts[M - 1];
@@ -752,24 +739,14 @@ __host__ __device__ constexpr int64_t hist_words(int64_t M, bool c16) {
 }
 // column-table entries (u16) in LDS
 __host__ __device__ constexpr int64_t tab_entries(bool p56, uint32_t S) { return p56 ? 1088 : (int64_t)S; }
-// KARMA_PROF_TABREP=1 (measurement variant): the column
-// table twice in LDS, lanes 32-63 reading the second copy, when it is small
-// (5p6's 1,088 entries), to test whether the lookup's bank collisions bound
-// the counting
-#ifndef KARMA_PROF_TABREP
-#define KARMA_PROF_TABREP 0
-#endif
-__host__ __device__ constexpr int tab_copies(int64_t t_pad) { return KARMA_PROF_TABREP && t_pad <= 4096 ? 2 : 1; }
 
-template <bool P56, bool C16>
 // 6 waves per SIMD (3 blocks per CU): fewer rows written at once write faster
 // than 8 waves (4 blocks) do, and the counting still hides under the writes:
 // profile 0.345-0.355 -> 0.335-0.337 ms at config 3 (round 3,
 // profiles/r03/measurements.md (ab_profwaves); 7 waves: 0.407, 5: 0.497, 4: 0.499 ms)
-#ifndef KARMA_PROF_WAVES
-#define KARMA_PROF_WAVES 6
-#endif
-__global__ void __launch_bounds__(kPBlock) __attribute__((amdgpu_waves_per_eu(KARMA_PROF_WAVES, KARMA_PROF_WAVES)))
+constexpr int kProfWaves = 6;
+template <bool P56, bool C16>
+__global__ void __launch_bounds__(kPBlock) __attribute__((amdgpu_waves_per_eu(kProfWaves, kProfWaves)))
 profile_wave_kernel(
     const uint32_t* __restrict__ packed, const uint16_t* __restrict__ mask, const uint8_t* __restrict__ has_exc,
     const int64_t* __restrict__ woff, const int64_t* __restrict__ off, const uint8_t* __restrict__ raw,
@@ -782,7 +759,6 @@ profile_wave_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
     uint16_t* tab = reinterpret_cast<uint16_t*>(lds);
     const int t_pad = (int)((tab_entries(P56, S) + 7) & ~7);
-    const int t_rep = tab_copies(t_pad);
     // LDS is laid out for M; with m_dev (the column table's count, not read
     // back to the host first) M is its capacity and the rows are dense
     const int h_words = (int)hist_words(M, C16);
@@ -790,7 +766,7 @@ profile_wave_kernel(
         M = *m_dev;
         ld = M;
     }
-    uint32_t* counts = lds + t_rep * t_pad / 2 + wave * (h_words + kProfWin);
+    uint32_t* counts = lds + t_pad / 2 + wave * (h_words + kProfWin);
     uint32_t* win = counts + h_words;
     uint16_t* mbuf = reinterpret_cast<uint16_t*>(win + 80);
     double* lut = reinterpret_cast<double*>(win);
@@ -804,15 +780,10 @@ profile_wave_kernel(
                 ord = (c6 >> 2) * 5u + 1u + (c6 & 3u);
             }
             tab[o] = (uint16_t)col_of_ord[ord];
-            if (t_rep == 2) tab[t_pad + o] = (uint16_t)col_of_ord[ord];
         }
     } else {
-        for (int o = threadIdx.x; o < S; o += blockDim.x) {
-            tab[o] = (uint16_t)col_of_ord[o];
-            if (t_rep == 2) tab[t_pad + o] = (uint16_t)col_of_ord[o];
-        }
+        for (int o = threadIdx.x; o < S; o += blockDim.x) tab[o] = (uint16_t)col_of_ord[o];
     }
-    if (t_rep == 2 && lane >= 32) tab += t_pad;  // this lane's copy
     for (int j = lane; j < h_words; j += 64) counts[j] = 0;  // write_row_wave clears it after each row
     __syncthreads();
     const int kmin = P56 ? 5 : k;
@@ -1262,8 +1233,8 @@ int kmer_finalize_device(karma_kmer_plan* p, int64_t* m_out, int64_t* m_host) {
     return KARMA_OK;
 }
 
-int kmer_profile_device_m(karma_kmer_plan* p, double* out_dev, const int64_t* m_dev, int headroom) {
-    return profile_rows(p, 0, p->store->n, out_dev, 0, 1, m_dev, headroom);
+int kmer_profile_device_m(karma_kmer_plan* p, double* out_dev, const int64_t* m_dev) {
+    return profile_rows(p, 0, p->store->n, out_dev, 0, 1, m_dev);
 }
 
 // the column keys of a plan finalized on the device, once M is known
@@ -1364,16 +1335,9 @@ static int profile_rows(karma_kmer_plan* p, int64_t lo, int64_t hi, double* out,
         // one round of resident blocks, each wave striding over contigs; u16
         // counters when no contig reaches 2^16 bases (a count is <= L)
         const bool p56 = p->kmode == KARMA_KMER_5P6;
-        const bool c16 = KARMA_PROF_C16 && c->max_len < 65536;
+        const bool c16 = c->max_len < 65536;
         const int64_t t_pad = (tab_entries(p56, p->S) + 7) & ~7;
-        size_t lds = (size_t)(t_pad * tab_copies(t_pad)) * 2 +
-                     (kPBlock / 64) * (size_t)(hist_words(M, c16) + kProfWin) * 4;
-        // KARMA_PROF_LDS_MIN (A/B): LDS per block at least this many bytes
-        static const size_t lds_min = [] {
-            const char* e = std::getenv("KARMA_PROF_LDS_MIN");
-            return e ? (size_t)std::atoll(e) : (size_t)0;
-        }();
-        lds = std::max(lds, lds_min);
+        const size_t lds = (size_t)t_pad * 2 + (kPBlock / 64) * (size_t)(hist_words(M, c16) + kProfWin) * 4;
 #define KARMA_WAVE_LAUNCH(P56, C16)                                                                              \
     do {                                                                                                         \
         const int g_ = resident_grid(ctx, reinterpret_cast<const void*>(&profile_wave_kernel<P56, C16>), kPBlock, \

@@ -58,10 +58,9 @@ struct StepStatus {
 };
 static_assert(sizeof(StepStatus) == 64, "status entry");
 
-#ifndef KARMA_EDGE_THREADS
-#define KARMA_EDGE_THREADS 512  // with 512-thread final blocks (graph_sets.hip kFT), profiles/r06/measurements.md (r06t)
-#endif
-constexpr int kET = KARMA_EDGE_THREADS;  // edge-stage tile (elements per block round)
+// edge-stage tile (elements per block round): 512 with 512-thread final blocks
+// (graph_sets.hip kFT), profiles/r06/measurements.md (r06t)
+constexpr int kET = 512;
 constexpr int kMaxRuns = 64;
 
 // ---- edge stage on device-sized lists ----------------------------------------
@@ -203,21 +202,14 @@ __global__ void __launch_bounds__(kET) step_edge_write_kernel(
 // 5 dependent loads), stages the windows in LDS, and places every element at
 // its rank in its own run plus its rank in each other run (stable: equal keys
 // of different runs end up adjacent, in run order).
-#ifndef KARMA_MARK_ONE
-#define KARMA_MARK_ONE 2  // deferred batches on one main stream (SetsJob::launch positions)
-#endif
-#ifndef KARMA_MARK_TWO
-#define KARMA_MARK_TWO 4  // deferred batches alternating two main streams (5, after the final kernel: 8-rank
-                          // strong preview 0.196 against 0.188 ms with the binned classify)
-#endif
-#ifndef KARMA_MARK_ONE_FLAGGED
-#define KARMA_MARK_ONE_FLAGGED 2  // ... on flagged records too.  3 (at once, beside classify, which reads half the
-                                  // bytes and is VALU-bound) measured 0.849 against 0.860 ms at config 3 (three
-                                  // reps each; after classify 0.928, after the final kernel 0.911), but then
-                                  // neither kernel's live time is its own (classify 0.65 ms live beside the
-                                  // profile): not kept for 1 %, profiles/r06/measurements.md (r06h)
-#endif
-constexpr int kMarkOne = KARMA_MARK_ONE, kMarkTwo = KARMA_MARK_TWO, kMarkOneFlagged = KARMA_MARK_ONE_FLAGGED;
+constexpr int kMarkOne = 2;  // deferred batches on one main stream (SetsJob::launch positions)
+constexpr int kMarkTwo = 4;  // deferred batches alternating two main streams (5, after the final kernel: 8-rank
+                             // strong preview 0.196 against 0.188 ms with the binned classify)
+constexpr int kMarkOneFlagged = 2;  // ... on flagged records too.  3 (at once, beside classify, which reads half the
+                                    // bytes and is VALU-bound) measured 0.849 against 0.860 ms at config 3 (three
+                                    // reps each; after classify 0.928, after the final kernel 0.911), but then
+                                    // neither kernel's live time is its own (classify 0.65 ms live beside the
+                                    // profile): not kept for 1 %, profiles/r06/measurements.md (r06h)
 constexpr int64_t kAltMaxRecords = int64_t(1) << 27;  // batches below this alternate main streams
 constexpr int kMT = 1024;       // tile elements (one round of tiles at the 8-rank preview's ~300k keys)
 constexpr int kMLds = 8192;     // staged window keys
@@ -570,11 +562,7 @@ struct karma_step {
     // then stays on the main stream, so no two busy streams share one of the
     // process's 4 hardware queues
     hipStream_t side_alt_s = nullptr;
-    int sides = 2;                // KARMA_STEP_SIDES=1: one side stream (A/B)
     int streams = 0;              // KARMA_STEP_STREAMS: 1 / 2 main streams (0: by the batch's size)
-    hipEvent_t ev = nullptr;      // side -> main join: the last deferred step's profile (one main stream)
-    bool ev_set = false;
-    bool join = false;            // KARMA_STEP_JOIN=1: join (A/B; measured slower, see run_deferred)
     // the profile (persistent; rows of n_loc x M, dense)
     DevArray<double> prof;
     // outputs of the last synchronous step
@@ -682,10 +670,8 @@ struct karma_step {
     int stall_s = 120;             // KARMA_STEP_STALL_S: a deferred status this late is KARMA_ERR_STALL
     // deferred records jobs use this step's own control blocks (tail[par].ctrl),
     // kept zero by the status kernel: no probe / clearing launch at their head,
-    // the relabel decided in classify (KARMA_STEP_OWN_CTRL=0: the job's own
-    // block and the probe kernel)
-    bool own_ctrl = true;
-    bool emu_xs = false;  // KARMA_STEP_EMU_XS=1 (A/B; see run_deferred)
+    // the relabel decided in classify (a job that needs a larger block than its
+    // tail's falls back to its own block and the probe kernel once)
     int lag = kLag;      // KARMA_STEP_LAG (A/B): deferred steps in flight before the host waits
     void* ring_mem = nullptr;      // this step's own mapped status ring (two steps on one context never share it)
     uint64_t fault_seq = 0;        // KARMA_STEP_FAULT_SEQ (tests only): this deferred step fails before its status
@@ -1074,12 +1060,11 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
     // the exchange stream carries the tail: with two main streams, and with
     // one communicator also behind one main stream (it then holds every
     // collective of the step, the presence all-gather included)
-    // (emulated ranks, KARMA_STEP_EMU_XS=1: the same stream layout as several
-    // processes, the tail on the exchange stream; its 8 more event calls per
-    // step cost more than the overlap gains: 8-rank strong preview 0.200 /
-    // 0.204 against 0.193 / 0.186 ms with the tail on the main stream, same box)
-    const bool xs_on = !sequential && s->xstream &&
-                       ((s->world > 1 && (two || s->one_comm)) || (s->world == 1 && s->emulate && s->emu_xs && two));
+    // (several processes only.  Emulated ranks keep the tail on the main
+    // stream: the exchange stream's 8 more event calls per step cost more than
+    // the overlap gains, 8-rank strong preview 0.200 / 0.204 against 0.193 /
+    // 0.186 ms, same box)
+    const bool xs_on = !sequential && s->xstream && s->world > 1 && (two || s->one_comm);
     if (two) ++s->n_two;
     if (xs_on) ++s->n_xs;
     const int par = sequential || !two ? 0 : (int)(seq & 1);
@@ -1092,14 +1077,9 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
         KARMA_HIP(hipStreamWaitEvent(ms, s->ev_tail[par], 0));
     }
     // One main stream (large batches): the records job does not wait for the
-    // previous batch's profile.  With KARMA_STEP_JOIN=1 it does (classify then
-    // never shares HBM with a profile): config 3 1.29-1.31 against 1.16-1.21 ms
-    // per step without the join (profiles/r04/measurements.md (ab_join)).
-    if (!two && !sequential && s->ev_set && s->join) {
-        if (counted_call("hipStreamWaitEvent")) ++t_hip_calls;
-        KARMA_HIP(hipStreamWaitEvent(ms, s->ev, 0));
-        s->ev_set = false;
-    }
+    // previous batch's profile.  Joining them (classify then never shares HBM
+    // with a profile) measured config 3 at 1.29-1.31 against 1.16-1.21 ms per
+    // step (profiles/r04/measurements.md (ab_join)).
     karma_step::Tail& tl = s->tail[par];
     // A failure between here and the status kernel's launch leaves this job's
     // flags, counters and block items in the tail's own control block (only
@@ -1115,7 +1095,7 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
         ~FailGuard() {
             if (!armed) return;
             for (hipStream_t q : {s->side_s, s->side_alt_s, s->main_s, s->alt_s}) (void)hipStreamSynchronize(q);
-            if (s->own_ctrl && tl.ctrl.ptr) {
+            if (tl.ctrl.ptr) {
                 (void)hipMemsetAsync(tl.ctrl.ptr, 0, tl.ctrl.n * 8, s->main_s);
                 (void)hipStreamSynchronize(s->main_s);
             }
@@ -1136,7 +1116,7 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
     SetsOpts jo;
     // the general-read branch: on the idle spare main stream with one main
     // stream; kept on the main stream with two (see side_alt_s)
-    jo.single_stream = two && s->sides == 2;
+    jo.single_stream = two;
     jo.fork = two ? nullptr : s->alt_s;
     // where the side stream's profile may start (SetsJob::launch): with one main
     // stream, after the code partition -- the profile's writes then share HBM
@@ -1144,15 +1124,15 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
     // batch's classify (config 3: 1.15 against 1.20-1.22 ms per step,
     // profiles/r04/measurements.md (ab_mark3)); with two, after the final kernel
     jo.mark = two ? kMarkTwo : flg ? kMarkOneFlagged : kMarkOne;
-    jo.ctrl = s->own_ctrl ? tl.ctrl.ptr : nullptr;  // zero: the last status kernel of this tail cleared it
-    jo.ctrl_words = s->own_ctrl ? (int64_t)tl.ctrl.n : 0;
+    jo.ctrl = tl.ctrl.ptr;  // zero: the last status kernel of this tail cleared it
+    jo.ctrl_words = (int64_t)tl.ctrl.n;
     RecIn rin;
     if (flg) rin.fw = rec;
     else rin.pr = reinterpret_cast<const uint2*>(rec);
     KARMA_TRY(sets_begin_deferred(ctx, rin, A, s->n_glob, jo, &job, &v));
     std::unique_ptr<SetsJob, void (*)(SetsJob*)> jg(job, sets_release);
     if (v.ctrl) ++s->n_own;
-    if (s->own_ctrl && !v.ctrl) {
+    if (!v.ctrl) {
         // the job needed a larger block than this tail's: grow it for the next
         // job on this tail (with every stream idle: the old block may still
         // be cleared by a status kernel), zeroed in stream order
@@ -1166,7 +1146,7 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
     // side stream: presence, column table (M stays on the device), then the
     // profile behind the graph's final kernel (sequential: all on the main
     // stream, every kernel alone on the chip -- the per-kernel timing pass)
-    hipStream_t const side = sequential ? ms : (par && s->sides == 2 && !xs_on ? s->side_alt_s : s->side_s);
+    hipStream_t const side = sequential ? ms : (par && !xs_on ? s->side_alt_s : s->side_s);
     int rc = KARMA_OK;
     {
         StreamScope on_side(ctx, side);
@@ -1214,18 +1194,7 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
             if (counted_call("hipStreamWaitEvent")) ++t_hip_calls;
             rc = hipStreamWaitEvent(side, ctx->mark_ev, 0) == hipSuccess ? KARMA_OK : KARMA_ERR_HIP;
         }
-        if (!rc && s->n_loc) {
-            // KARMA_STEP_HEADROOM (A/B): profile blocks per CU left free for the
-            // main stream's kernels (one main stream only)
-            static const int headroom = getenv("KARMA_STEP_HEADROOM") ? atoi(getenv("KARMA_STEP_HEADROOM")) : 0;
-            rc = kmer_profile_device_m(plan, tl.prof.ptr, m_dev, two || sequential ? 0 : headroom);
-        }
-        if (!rc && !two && !sequential && s->join) {
-            if (!s->ev && hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) rc = KARMA_ERR_HIP;
-            if (counted_call("hipEventRecord")) ++t_hip_calls;
-            if (!rc) rc = hipEventRecord(s->ev, side) == hipSuccess ? KARMA_OK : KARMA_ERR_HIP;
-            s->ev_set = !rc;
-        }
+        if (!rc && s->n_loc) rc = kmer_profile_device_m(plan, tl.prof.ptr, m_dev);
         if (plan) karma_kmer_plan_destroy(plan);  // its buffers return to the side stream's cache
     }
     KARMA_TRY(rc);
@@ -1362,13 +1331,9 @@ int karma_step_create(karma_ctx* ctx, karma_comm* comm, karma_comm* side_comm, i
     s->nranks = nranks;
     s->emulate = world == 1 && nranks > 1 ? nranks : 0;
     if (const char* e = getenv("KARMA_STEP_STREAMS")) s->streams = atoi(e) == 1 ? 1 : atoi(e) == 2 ? 2 : 0;
-    if (const char* e = getenv("KARMA_STEP_JOIN")) s->join = atoi(e) != 0;  // A/B only
-    if (const char* e = getenv("KARMA_STEP_SIDES")) s->sides = atoi(e) == 1 ? 1 : 2;
     if (const char* e = getenv("KARMA_STEP_DEFER_RANKS")) s->defer_ranks = atoi(e) != 0;
     if (const char* e = getenv("KARMA_STEP_XSTREAM")) s->xstream = atoi(e) != 0;
     if (const char* e = getenv("KARMA_STEP_STALL_S")) s->stall_s = std::max(1, atoi(e));
-    if (const char* e = getenv("KARMA_STEP_OWN_CTRL")) s->own_ctrl = atoi(e) != 0;
-    if (const char* e = getenv("KARMA_STEP_EMU_XS")) s->emu_xs = atoi(e) != 0;
     if (const char* e = getenv("KARMA_STEP_LAG")) s->lag = std::max(1, std::min(kRing / 2, atoi(e)));
     if (const char* e = getenv("KARMA_STEP_FAULT_SEQ")) s->fault_seq = strtoull(e, nullptr, 10);
     s->n_glob = n_glob;
@@ -1382,10 +1347,9 @@ int karma_step_create(karma_ctx* ctx, karma_comm* comm, karma_comm* side_comm, i
     // blocks dispatch first when CUs free up beside the side-stream profile
     KARMA_HIP(hipStreamCreateWithPriority(&s->main_s, hipStreamNonBlocking, hi));
     KARMA_HIP(hipStreamCreateWithPriority(&s->alt_s, hipStreamNonBlocking, hi));
-    // KARMA_STEP_SIDE_PRIO=1 (A/B): the side streams at the main streams' priority
-    const int side_prio = getenv("KARMA_STEP_SIDE_PRIO") && atoi(getenv("KARMA_STEP_SIDE_PRIO")) ? hi : 0;
-    KARMA_HIP(hipStreamCreateWithPriority(&s->side_s, hipStreamNonBlocking, side_prio));
-    KARMA_HIP(hipStreamCreateWithPriority(&s->side_alt_s, hipStreamNonBlocking, side_prio));
+    // the side streams at the default priority
+    KARMA_HIP(hipStreamCreateWithPriority(&s->side_s, hipStreamNonBlocking, 0));
+    KARMA_HIP(hipStreamCreateWithPriority(&s->side_alt_s, hipStreamNonBlocking, 0));
     // the status ring in mapped coherent host memory of this step's own: a
     // second live step on the context numbers its steps from 1 too, and a
     // shared ring would hand it this step's verdicts
@@ -1583,8 +1547,7 @@ int karma_step_destroy(karma_step* s) {
     bury(s, true);
     for (auto& ev : s->grave_ev)
         if (ev) hipEventDestroy(ev);
-    for (hipEvent_t ev : {s->ev, s->ev_rec, s->ev_sync, s->ev_tail[0], s->ev_tail[1], s->ev_pres, s->ev_pres2,
-                          s->ev_pre})
+    for (hipEvent_t ev : {s->ev_rec, s->ev_sync, s->ev_tail[0], s->ev_tail[1], s->ev_pres, s->ev_pres2, s->ev_pre})
         if (ev) hipEventDestroy(ev);
     if (s->graves_h) hipHostFree(s->graves_h);
     if (s->ring_mem) hipHostFree(s->ring_mem);

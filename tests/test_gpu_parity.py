@@ -385,7 +385,7 @@ def test_records_compact_reads_of_9_to_16_at_chunk_edges():
 @pytest.mark.parametrize("n", [3000, 1_200_000, 2_200_000])  # binned, compact unbinned, no compact path
 def test_flagged_records_sixteen_per_lane(n):
     """Flagged classify steps hold 16 records per lane (graph_sets.hip
-    KARMA_FLAG_RPL): reads of 9..16 records inside one lane (compact: a code;
+    classify2_kernel's RPL): reads of 9..16 records inside one lane (compact: a code;
     general: the big list, as the general path reads 8), a read filling a lane
     exactly (a tail seen whole), reads of 17..40 records (lanes without a
     start), and runs of one-record reads (1,024 codes per step: the staging
