@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "karma_internal.h"
+#include "sets_ctrl.h"
 
 using namespace karma;
 
@@ -1077,8 +1078,8 @@ classify2_kernel(ClassArgs P, BinArgs Q) {
     }
     if (lane == 0) {
         const ClassArgs& Pa = P;
-        if (bad_order) Pa.flags[0] = 1;
-        if (bad_contig) Pa.flags[1] = 1;
+        if (bad_order) Pa.flags[kFlagOrder] = 1;
+        if (bad_contig) Pa.flags[kFlagContigRange] = 1;
         // kVotes, or half the voting chunks of a small job
         const int64_t voters = ((Pa.A + Pa.chunk - 1) / Pa.chunk + kVoteStride - 1) / kVoteStride;
         const unsigned need = (unsigned)min<int64_t>(kVotes, (voters + 1) / 2);
@@ -1158,9 +1159,9 @@ __global__ void __launch_bounds__(kGW) general_kernel(RecIn rec, int64_t A, uint
     if (lane == 0) {
         n_pairs[chunk] = np;
         if (np) atomicAdd(blk_items + chunk / lists_per_block, (unsigned long long)np);
-        if (full) flags[2] = 1;  // the host reruns with room for every pair
+        if (full) flags[kFlagPairCap] = 1;  // the host reruns with room for every pair
     }
-    if (bad) flags[1] = 1;
+    if (bad) flags[kFlagContigRange] = 1;
     }
 }
 
@@ -2475,11 +2476,12 @@ int records_to_pairs_wide(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, karma
     KARMA_TRY(blk_items.alloc(ctx, 2 * n_chunks));
     KARMA_TRY(widths.alloc(ctx, n_chunks + 1));
     KARMA_TRY(off.alloc(ctx, n_chunks + 1));
-    KARMA_TRY(ctrl.alloc(ctx, 4));  // flags[4] | counters[3] (big reads) | spare
-    int* const flags = reinterpret_cast<int*>(ctrl.ptr);
-    unsigned* const counters = reinterpret_cast<unsigned*>(ctrl.ptr + 2);
+    constexpr int64_t kCw = CtrlLayout::small_words;  // the flags and the big-reads counter
+    KARMA_TRY(ctrl.alloc(ctx, kCw));
+    int* const flags = reinterpret_cast<int*>(ctrl.ptr + CtrlLayout::flags);
+    unsigned* const counters = reinterpret_cast<unsigned*>(ctrl.ptr + CtrlLayout::counters);
     void* hpin = nullptr;
-    KARMA_TRY(ctx_pinned(ctx, 5 * 8, &hpin));
+    KARMA_TRY(ctx_pinned(ctx, (kCw + 1) * 8, &hpin));  // ... and the pair total behind them
     int64_t* const h = static_cast<int64_t*>(hpin);
     int64_t pcap = kCChunk / 8;
     DevArray<uint64_t> plist;
@@ -2487,7 +2489,7 @@ int records_to_pairs_wide(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, karma
     unsigned n_big = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         KARMA_TRY(plist.alloc(ctx, n_chunks * pcap));
-        KARMA_HIP(hipMemsetAsync(ctrl.ptr, 0, 4 * 8, ctx->stream));
+        KARMA_HIP(hipMemsetAsync(ctrl.ptr, 0, kCw * 8, ctx->stream));
         KARMA_HIP(hipMemsetAsync(blk_items.ptr, 0, 2 * n_chunks * 8, ctx->stream));
         KARMA_HIP(hipMemsetAsync(n_gen.ptr, 0, n_chunks * 4, ctx->stream));
         if (A > 0) {
@@ -2508,15 +2510,16 @@ int records_to_pairs_wide(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, karma
         KARMA_LAUNCH(ctx, "widen_counts", widen_counts_kernel, grid_n(n_chunks + 1), 256, 0, n_pl.ptr, n_chunks,
                      widths.ptr);
         KARMA_TRY(scan_excl_i64(ctx, widths.ptr, off.ptr, n_chunks + 1));
-        KARMA_HIP(hipMemcpyAsync(h, ctrl.ptr, 4 * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KARMA_HIP(hipMemcpyAsync(h + 4, off.ptr + n_chunks, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KARMA_HIP(hipMemcpyAsync(h, ctrl.ptr, kCw * 8, hipMemcpyDeviceToHost, ctx->stream));
+        KARMA_HIP(hipMemcpyAsync(h + kCw, off.ptr + n_chunks, 8, hipMemcpyDeviceToHost, ctx->stream));
         KARMA_HIP(hipStreamSynchronize(ctx->stream));
-        const int* hf = reinterpret_cast<const int*>(h);
-        KARMA_CHECK(!hf[0], KARMA_ERR_UNSORTED, "records are not grouped by read (read ids decrease)");
-        KARMA_CHECK(!hf[1], KARMA_ERR_ARG, "a record's contig index is >= n_contigs (%lld)", (long long)N);
-        n_big = reinterpret_cast<const unsigned*>(h + 2)[0];
-        P = h[4];
-        if (!hf[2]) break;
+        const int* hf = reinterpret_cast<const int*>(h + CtrlLayout::flags);
+        KARMA_CHECK(!hf[kFlagOrder], KARMA_ERR_UNSORTED, "records are not grouped by read (read ids decrease)");
+        KARMA_CHECK(!hf[kFlagContigRange], KARMA_ERR_ARG, "a record's contig index is >= n_contigs (%lld)",
+                    (long long)N);
+        n_big = reinterpret_cast<const unsigned*>(h + CtrlLayout::counters)[kCtrBigReads];
+        P = h[kCw];
+        if (!hf[kFlagPairCap]) break;
         KARMA_CHECK(attempt == 0, KARMA_ERR_STATE, "pair list capacity exceeded twice");
         pcap = kCChunk * 9 / 2;  // every read with <= 8 records fits
     }
@@ -2669,13 +2672,9 @@ __global__ void relabel_back_kernel(uint64_t* __restrict__ keys, int64_t n, cons
 // block readback; end() waits, checks, reruns on a full pair list, and
 // assembles.  Between the two the host may enqueue unrelated work (the k-mer
 // profile on a side stream).
+// where side-stream work (the k-mer profile) may start by default, see
+// SetsJob::launch and mark_at()
 constexpr int kMarkAt = 5;
-// where side-stream work (the k-mer profile) may start, see SetsJob::launch;
-// KARMA_MARK_AT in the environment overrides the default (scheduling only:
-// every position runs the same kernels)
-// the general-read branch on the context's fork stream beside the code branch
-// (KARMA_FORK=0 in the environment: both branches in order on one stream;
-// scheduling only, the same kernels run)
 // the binned classify where it applies (KARMA_BIN=0 in the environment: the
 // code partition instead, A/B and tests; read per job)
 bool bin_on() {
@@ -2689,6 +2688,9 @@ uint32_t back_list_cap() {
     const int v = e ? std::atoi(e) : kBackList;
     return (uint32_t)std::max(0, std::min(v, kBackList));
 }
+// the general-read branch on a fork stream beside the code branch
+// (KARMA_FORK=0 in the environment: both branches in order on one stream;
+// scheduling only, the same kernels run)
 bool fork_on() {
     static const bool on = [] {
         const char* e = std::getenv("KARMA_FORK");
@@ -2713,8 +2715,9 @@ int64_t chunk_records(const karma_ctx* ctx, int64_t A) {
     const int64_t slots = (int64_t)ctx->cu_count * 16;
     return ceil_div(A, kCChunk) < 4 * slots ? kCChunk / 2 : kCChunk;
 }
-// KARMA_MARK_AT in the environment wins; else the caller's choice
-// (SetsOpts::mark, the native step's deferred batches), else the default
+// KARMA_MARK_AT in the environment wins (scheduling only: every position
+// runs the same kernels); else the caller's choice (SetsOpts::mark, the
+// native step's deferred batches), else the default
 int mark_at(int asked) {
     static const int env = [] {
         const char* e = std::getenv("KARMA_MARK_AT");
@@ -2745,10 +2748,9 @@ struct SetsJob {
     int64_t n_pblk = 0;
     DevArray<uint32_t> codes, n_codes, n_gen, n_pl;
     DevArray<int64_t> big_list;
-    // control block, cleared by one memset and read back by one copy:
-    // flags[4] | counters[3] (big reads, code flushes, pair flushes) | spare[2]
-    // | pairs per bucket[B+1] | their exclusive scan[B+1] | overflow[B]
-    int64_t ctrl_words = 0;
+    // control block, cleared by one memset, its head read back by one copy; its regions
+    // and the names of its flags and counters (relabel and vote included): sets_ctrl.h
+    CtrlLayout cl{0, 0, 0};
     DevArray<int64_t> ctrl;
     int64_t* cb = nullptr;  // the control block: ctrl, or the caller's zeroed one (ext)
     bool ext = false;
@@ -2821,34 +2823,33 @@ int SetsJob::setup() {
     KARMA_TRY(n_pl.alloc(ctx, n_chunks));
     KARMA_TRY(big_list.alloc(ctx, A / (kMaxFast + 1) + 1));
     pcap = chunk / 8;
-    ctrl_words = 6 + 2 * (int64_t)(B + 1) + ceil_div(B, 8) + (int64_t)split_b.size();
     // one allocation (and one memset per attempt) for the control block and
     // the per-partition-block item counts behind it
-    const int64_t cw_total = ctrl_words + 2 * n_pblk + B;
+    cl = CtrlLayout(B, (int64_t)split_b.size(), n_pblk);
     // a deferred job may take the caller's zeroed block (SetsOpts::ctrl)
-    ext = deferred && opts.ctrl && opts.ctrl_words >= cw_total;
+    ext = deferred && opts.ctrl && opts.ctrl_words >= cl.total;
     static const bool debug_ctrl = std::getenv("KARMA_DEBUG_CTRL") != nullptr;
     if (debug_ctrl)
         std::fprintf(stderr, "[karma] records job: deferred %d, caller block %p (%lld words), needs %lld: %s\n",
-                     (int)deferred, (void*)opts.ctrl, (long long)opts.ctrl_words, (long long)cw_total,
+                     (int)deferred, (void*)opts.ctrl, (long long)opts.ctrl_words, (long long)cl.total,
                      ext ? "caller's" : "own");
     if (ext) {
         cb = opts.ctrl;
     } else {
-        KARMA_TRY(ctrl.alloc(ctx, cw_total));
+        KARMA_TRY(ctrl.alloc(ctx, cl.total));
         cb = ctrl.ptr;
     }
-    blk_items = reinterpret_cast<unsigned long long*>(cb + ctrl_words);
-    lb = reinterpret_cast<uint64_t*>(cb + ctrl_words + 2 * n_pblk);
-    flags = reinterpret_cast<int*>(cb);
-    counters = reinterpret_cast<unsigned*>(cb + 2);
-    n_per = cb + 6;
-    dst = n_per + (B + 1);
-    ovf = reinterpret_cast<uint8_t*>(dst + (B + 1));
-    split_loc = dst + (B + 1) + ceil_div(B, 8);
+    blk_items = reinterpret_cast<unsigned long long*>(cb + cl.blk_items);
+    lb = reinterpret_cast<uint64_t*>(cb + cl.lb);
+    flags = reinterpret_cast<int*>(cb + cl.flags);
+    counters = reinterpret_cast<unsigned*>(cb + cl.counters);
+    n_per = cb + cl.n_per;
+    dst = cb + cl.dst;
+    ovf = reinterpret_cast<uint8_t*>(cb + cl.ovf);
+    split_loc = cb + cl.split_loc;
     if (!deferred) {
         void* hpin = nullptr;
-        KARMA_TRY(ctx_job_pinned(ctx, ctrl_words * 8, &hpin));
+        KARMA_TRY(ctx_job_pinned(ctx, cl.readback * 8, &hpin));
         hctrl = static_cast<const int64_t*>(hpin);
     }
     // code stream: <= one code per record + < 8 padding codes per run; a block
@@ -2923,7 +2924,7 @@ int SetsJob::launch() {
     // already on the first attempt, and classify decides the relabel itself
     const bool fresh_ext = ext && attempt == 0 && !relabeled;
     const bool probe = A > 0 && !relabeled && !fresh_ext;
-    if (!probe && !fresh_ext) KARMA_HIP(hipMemsetAsync(cb, 0, (ctrl_words + 2 * n_pblk + B) * 8, ctx->stream));
+    if (!probe && !fresh_ext) KARMA_HIP(hipMemsetAsync(cb, 0, cl.total * 8, ctx->stream));
     if (append) KARMA_HIP(hipMemsetAsync(blk_hist.ptr, 0, n_pblk * g.Bc * 4, ctx->stream));
     // where side-stream work (the k-mer profile) may start: 5 = after the final
     // kernel, beside the control-block readback (default; 0.283 against 0.291
@@ -2974,11 +2975,11 @@ int SetsJob::launch() {
             // a probe of the reads decides: when many span more than 4 contig
             // ids, this pass is skipped and a relabelled rerun follows
             KARMA_LAUNCH(ctx, "relabel_probe", relabel_probe_kernel, 1, kRelabelProbes, 0, rec, A, (uint32_t)N,
-                         counters + 3, reinterpret_cast<uint64_t*>(cb), (int64_t)(ctrl_words + 2 * n_pblk + B));
-            C.skip = counters + 3;
+                         counters + kCtrRelabel, reinterpret_cast<uint64_t*>(cb), cl.total);
+            C.skip = counters + kCtrRelabel;
         } else if (fresh_ext) {
-            C.skip = counters + 3;
-            C.vote = counters + 4;
+            C.skip = counters + kCtrRelabel;
+            C.vote = counters + kCtrVote;
         }
         KARMA_TRY(classify(0, n_chunks));
     }
@@ -2988,8 +2989,8 @@ int SetsJob::launch() {
         KARMA_HIP(hipMemsetAsync(n_gen.ptr, 0, n_chunks * 4, ctx->stream));
         if (bin) KARMA_HIP(hipMemsetAsync(bhdr.ptr, 0, n_chunks * 16 * kBinHdr, ctx->stream));
     }
-    const RunDir cdir{cf_base.ptr, cf_off.ptr, counters + 1, blk_items};
-    pdir = RunDir{pf_base.ptr, pf_off.ptr, counters + 2, blk_items + n_pblk};
+    const RunDir cdir{cf_base.ptr, cf_off.ptr, counters + kCtrCodeFlushes, blk_items};
+    pdir = RunDir{pf_base.ptr, pf_off.ptr, counters + kCtrPairFlushes, blk_items + n_pblk};
     // Two independent branches after classify, joined by the final kernel:
     // general reads -> pair lists -> pair partition -> pair reduce, and the
     // code partition -> code reduce.  The first (three short kernels) runs on
@@ -3009,7 +3010,8 @@ int SetsJob::launch() {
         StreamScope on_fork(ctx, fork_s);
         KARMA_LAUNCH(ctx, "graph_general", general_kernel, general_grid(ctx, n_chunks), kGW, 0, rec, A, (uint32_t)N,
                      codes.ptr, n_gen.ptr, n_chunks, plist.ptr, pcap, n_pl.ptr, blk_items + n_pblk, lpb, flags,
-                     relabeled ? (const uint32_t*)remap_map.ptr : nullptr, (const unsigned*)(counters + 3), chunk);
+                     relabeled ? (const uint32_t*)remap_map.ptr : nullptr,
+                     (const unsigned*)(counters + kCtrRelabel), chunk);
         if (wide_p)
             KARMA_LAUNCH(ctx, "graph_pair_partition", partition_kernel<PairStreamWide>, n_pblk, kPT, 0, plist.ptr,
                          pcap, n_pl.ptr, n_chunks, lpb, g, pent.ptr, pdir);
@@ -3034,10 +3036,10 @@ int SetsJob::launch() {
         uint16_t* const trash = cent.ptr + (ccap + 7) / 8 * 8;
         if (append && wide_c)
             KARMA_LAUNCH(ctx, "graph_code_partition", code_append_kernel<kMaxBc>, n_pblk, kPT, 0, codes.ptr, chunk,
-                         n_codes.ptr, n_chunks, lpb, g, blk_hist.ptr, cent.ptr, trash, cdir, flags + 3);
+                         n_codes.ptr, n_chunks, lpb, g, blk_hist.ptr, cent.ptr, trash, cdir, flags + kFlagPartition);
         else if (append)
-            KARMA_LAUNCH(ctx, "graph_code_partition", code_append_kernel<kNarrowBc>, n_pblk, kPT, 0, codes.ptr,
-                         chunk, n_codes.ptr, n_chunks, lpb, g, blk_hist.ptr, cent.ptr, trash, cdir, flags + 3);
+            KARMA_LAUNCH(ctx, "graph_code_partition", code_append_kernel<kNarrowBc>, n_pblk, kPT, 0, codes.ptr, chunk,
+                         n_codes.ptr, n_chunks, lpb, g, blk_hist.ptr, cent.ptr, trash, cdir, flags + kFlagPartition);
         else if (wide_c)
             KARMA_LAUNCH(ctx, "graph_code_partition", partition_kernel<CodeStreamWide>, n_pblk, kPT, 0, codes.ptr,
                          chunk, n_codes.ptr, n_chunks, lpb, g, cent.ptr, cdir);
@@ -3064,7 +3066,7 @@ int SetsJob::launch() {
                      ovf, sa, lb, dst);
     KARMA_TRY(mark(5));  // after the final kernel, before the control-block readback
     if (!deferred)
-        KARMA_HIP(hipMemcpyAsync(const_cast<int64_t*>(hctrl), cb, ctrl_words * 8, hipMemcpyDeviceToHost,
+        KARMA_HIP(hipMemcpyAsync(const_cast<int64_t*>(hctrl), cb, cl.readback * 8, hipMemcpyDeviceToHost,
                                  ctx->stream));
     return KARMA_OK;
 }
@@ -3097,46 +3099,48 @@ int SetsJob::relabel() {
 }
 
 int SetsJob::finish(karma_pairs* out) {
-    unsigned hc[4] = {0, 0, 0, 0};
+    unsigned hc[kCtrlCounters] = {};
     std::vector<uint8_t> hovf(B);
     int64_t U = 0;
     for (;;) {
         // the one synchronisation of the common path
         KARMA_HIP(hipStreamSynchronize(ctx->stream));
-        const int* hf = reinterpret_cast<const int*>(hctrl);
-        std::memcpy(hc, hctrl + 2, sizeof hc);
-        std::memcpy(hovf.data(), hctrl + 6 + 2 * (B + 1), B);
-        U = hctrl[6 + (B + 1) + B];
-        KARMA_CHECK(!hf[0], KARMA_ERR_UNSORTED, "records are not grouped by read (read ids decrease)");
-        KARMA_CHECK(!hf[1], KARMA_ERR_ARG, "a record's contig index is >= n_contigs (%lld)", (long long)N);
-        KARMA_CHECK(!hf[3], KARMA_ERR_STATE, "code partition: block counts disagree with the classify histogram");
-        if (!relabeled && hc[3]) {  // most reads were general: rerun on relabelled contigs
+        const int* hf = reinterpret_cast<const int*>(hctrl + cl.flags);
+        std::memcpy(hc, hctrl + cl.counters, sizeof hc);
+        std::memcpy(hovf.data(), hctrl + cl.ovf, B);
+        U = hctrl[cl.list_len];
+        KARMA_CHECK(!hf[kFlagOrder], KARMA_ERR_UNSORTED, "records are not grouped by read (read ids decrease)");
+        KARMA_CHECK(!hf[kFlagContigRange], KARMA_ERR_ARG, "a record's contig index is >= n_contigs (%lld)",
+                    (long long)N);
+        KARMA_CHECK(!hf[kFlagPartition], KARMA_ERR_STATE,
+                    "code partition: block counts disagree with the classify histogram");
+        if (!relabeled && hc[kCtrRelabel]) {  // most reads were general: rerun on relabelled contigs
             KARMA_TRY(relabel());
             relabeled = true;
             KARMA_TRY(launch());
             continue;
         }
-        if (!hf[2]) break;
+        if (!hf[kFlagPairCap]) break;
         KARMA_CHECK(attempt == 0, KARMA_ERR_STATE, "pair list capacity exceeded twice");
         attempt = 1;
         pcap = chunk * 9 / 2;  // every read with <= 8 records fits
         KARMA_TRY(launch());
     }
-    const unsigned n_big = hc[0];
+    const unsigned n_big = hc[kCtrBigReads];
     if (std::getenv("KARMA_DEBUG_GEN")) {  // diagnostic: reads on the general path, big reads
         std::vector<uint32_t> hg(n_chunks);
         KARMA_HIP(hipMemcpy(hg.data(), n_gen.ptr, n_chunks * 4, hipMemcpyDeviceToHost));
         uint64_t tot = 0;
         for (uint32_t x : hg) tot += x;
         std::fprintf(stderr, "[karma] general reads %llu, big reads %u, pair flushes %u\n", (unsigned long long)tot,
-                     n_big, hc[2]);
+                     n_big, hc[kCtrPairFlushes]);
     }
     DevArray<const uint64_t*> pk;  // per-bucket list overrides (overflowed buckets only)
     DevArray<const int64_t*> pc;
     DevArray<int64_t> src_off;     // where the final kernel put each other bucket's list
     std::vector<std::unique_ptr<DevArray<uint64_t>>> keep_k;
     std::vector<std::unique_ptr<DevArray<int64_t>>> keep_c;
-    const int64_t widen_threads = std::max<int64_t>(hc[2], (int64_t(8) << g.bw) + 24);
+    const int64_t widen_threads = std::max<int64_t>(hc[kCtrPairFlushes], (int64_t(8) << g.bw) + 24);
     bool any_ovf = false;
     for (int b = 0; b < B; ++b) {
         if (!hovf[b]) continue;
@@ -3199,8 +3203,8 @@ int SetsJob::finish(karma_pairs* out) {
         KARMA_TRY(finish_pairs(ctx, rec, A, N, big_list.ptr, n_big, mk, mc, U, out));
         if (!split_b.empty() && !any_ovf && n_big == 0) {
             // the owners' slice starts, from the final kernel's in-bucket counts
-            const int64_t* h_dst = hctrl + 6 + (B + 1);
-            const int64_t* h_loc = h_dst + (B + 1) + ceil_div(B, 8);
+            const int64_t* h_dst = hctrl + cl.dst;
+            const int64_t* h_loc = hctrl + cl.split_loc;
             out->split_bounds = split_b;
             out->split_starts.resize(split_b.size());
             for (size_t r = 0; r < split_b.size(); ++r) {
@@ -3287,7 +3291,7 @@ int sets_begin_deferred(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, const S
     v->counters = j->counters;
     v->ovf = j->ovf;
     v->ctrl = j->ext ? j->cb : nullptr;
-    v->ctrl_need = j->ctrl_words + 2 * j->n_pblk + j->B;
+    v->ctrl_need = j->cl.total;
     return KARMA_OK;
 }
 

@@ -319,8 +319,8 @@ struct SetsDeferred {
     const int64_t* split_loc = nullptr;  // per split bound: keys of its bucket below it
     std::vector<int64_t> split_b;     // the split bounds (host)
     int B = 0, bw = 0;
-    const int* flags = nullptr;       // [0] unsorted, [1] contig range, [2] pair capacity, [3] partition check
-    const unsigned* counters = nullptr;  // [0] big reads, [3] relabel vote
+    const int* flags = nullptr;       // indexed by CtrlFlag (sets_ctrl.h)
+    const unsigned* counters = nullptr;  // indexed by CtrlCounter
     const uint8_t* ovf = nullptr;     // per bucket: overflowed the LDS tables (generic path needed)
     int64_t* ctrl = nullptr;          // the caller's control block when the job used it (SetsOpts::ctrl), else null
     int64_t ctrl_need = 0;            // words of control block the job needed (a larger SetsOpts::ctrl next time)

@@ -33,11 +33,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <initializer_list>
 #include <memory>
 #include <thread>
 #include <vector>
 
 #include "karma_internal.h"
+#include "sets_ctrl.h"
+#include "step_schedule.h"
 
 using namespace karma;
 
@@ -47,11 +50,13 @@ constexpr int kRing = 64;  // status entries in the mapped slot (64 B each)
 constexpr int kLag = 3;    // deferred steps the host may have in flight (two main streams alternate)
 
 // One deferred step's status, written by step_status_kernel (seq last).
+// StepStatus::err bits (step_status_kernel sets them, check_entry reads them)
+enum StepErr : int64_t { kErrOrder = 1, kErrRange = 2, kErrPartition = 4, kErrZeroTotal = 8, kErrMergeOrder = 16 };
 struct StepStatus {
     uint64_t seq;
     int64_t slow;   // bits: 1 relabel, 2 pair capacity, 4 big reads, 8 bucket overflow, 16 exchange slots,
                     // 32 another rank's step needs the general path
-    int64_t err;    // bits: 1 unsorted records, 2 contig range, 4 partition check, 8 zero total, 16 merge order
+    int64_t err;    // StepErr: unsorted records, contig range, partition check, zero total, merge order
     int64_t U;      // pairs of the local list
     int64_t E;      // edges
     int64_t pad[3];
@@ -202,15 +207,6 @@ __global__ void __launch_bounds__(kET) step_edge_write_kernel(
 // 5 dependent loads), stages the windows in LDS, and places every element at
 // its rank in its own run plus its rank in each other run (stable: equal keys
 // of different runs end up adjacent, in run order).
-constexpr int kMarkOne = 2;  // deferred batches on one main stream (SetsJob::launch positions)
-constexpr int kMarkTwo = 4;  // deferred batches alternating two main streams (5, after the final kernel: 8-rank
-                             // strong preview 0.196 against 0.188 ms with the binned classify)
-constexpr int kMarkOneFlagged = 2;  // ... on flagged records too.  3 (at once, beside classify, which reads half the
-                                    // bytes and is VALU-bound) measured 0.849 against 0.860 ms at config 3 (three
-                                    // reps each; after classify 0.928, after the final kernel 0.911), but then
-                                    // neither kernel's live time is its own (classify 0.65 ms live beside the
-                                    // profile): not kept for 1 %, profiles/r06/measurements.md (r06h)
-constexpr int64_t kAltMaxRecords = int64_t(1) << 27;  // batches below this alternate main streams
 constexpr int kMT = 1024;       // tile elements (one round of tiles at the 8-rank preview's ~300k keys)
 constexpr int kMLds = 8192;     // staged window keys
 constexpr int kMFast = 8;       // up to this many runs: every element's searches run in lockstep
@@ -459,7 +455,8 @@ __global__ void __launch_bounds__(256) step_pack_kernel(const uint64_t* __restri
     }
     if (threadIdx.x == 0) {
         over = 0;
-        slow = counters[3] || flags[2] || counters[0];  // the status kernel's slow words, less the slots
+        // the status kernel's slow words, less the slots
+        slow = counters[kCtrRelabel] || flags[kFlagPairCap] || counters[kCtrBigReads];
     }
     __syncthreads();
     if (threadIdx.x < (unsigned)nr && ro[threadIdx.x + 1] - ro[threadIdx.x] > slot - 1) over = 1;
@@ -507,8 +504,9 @@ __global__ void step_status_kernel(const int* flags, const unsigned* counters, c
     for (int b = threadIdx.x; b < B; b += blockDim.x)
         if (ovf[b]) any_ovf = 1;
     if (threadIdx.x == 0) {
-        words[0] = (int64_t)flags[0] | (int64_t)flags[1] << 8 | (int64_t)flags[2] << 16 | (int64_t)flags[3] << 24;
-        words[1] = (int64_t)(counters[0] != 0) | (int64_t)(counters[3] != 0) << 1;
+        words[0] = (int64_t)flags[kFlagOrder] | (int64_t)flags[kFlagContigRange] << 8 |
+                   (int64_t)flags[kFlagPairCap] << 16 | (int64_t)flags[kFlagPartition] << 24;
+        words[1] = (int64_t)(counters[kCtrBigReads] != 0) | (int64_t)(counters[kCtrRelabel] != 0) << 1;
         words[2] = dst[B];
     }
     __syncthreads();
@@ -516,20 +514,20 @@ __global__ void step_status_kernel(const int* flags, const unsigned* counters, c
         for (int64_t i = threadIdx.x; i < n_ctrl; i += blockDim.x) ctrl[i] = 0;
     if (threadIdx.x != 0) return;
     const int fw = (int)words[0];
-    const int f0 = fw & 255, f1 = (fw >> 8) & 255, f2 = (fw >> 16) & 255, f3 = (fw >> 24) & 255;
-    const bool c0 = words[1] & 1, c3 = (words[1] >> 1) & 1;
+    const int f_order = fw & 255, f_range = (fw >> 8) & 255, f_cap = (fw >> 16) & 255, f_part = (fw >> 24) & 255;
+    const bool c_big = words[1] & 1, c_relabel = (words[1] >> 1) & 1;
     int64_t slow = 0, err = 0;
-    if (c3) slow |= 1;
-    if (f2) slow |= 2;
-    if (c0) slow |= 4;
+    if (c_relabel) slow |= 1;
+    if (f_cap) slow |= 2;
+    if (c_big) slow |= 4;
     if (any_ovf) slow |= 8;
-    if (f0) err |= 1;
-    if (f1) err |= 2;
-    if (f3) err |= 4;
-    if (est[0]) err |= 8;
-    if (est[1]) err |= 2;  // a key past the contig range
+    if (f_order) err |= kErrOrder;
+    if (f_range) err |= kErrRange;
+    if (f_part) err |= kErrPartition;
+    if (est[0]) err |= kErrZeroTotal;
+    if (est[1]) err |= kErrRange;  // a key past the contig range
     if (merge_bad) {
-        if (*merge_bad & 1) err |= 16;
+        if (*merge_bad & 1) err |= kErrMergeOrder;
         if (*merge_bad & 2) slow |= 16;  // the exchange's slots were too small
         if (*merge_bad & 4) slow |= 32;  // another rank's step needs the general path
         *merge_bad = 0;  // cleared for the next step's merge (stream order)
@@ -679,15 +677,31 @@ struct karma_step {
 
 namespace {
 
+// Every stream of this step idle: its four streams, waited for in the caller's
+// order (a stream not created yet is skipped).  quiet: failures are ignored
+// (and the calls not counted), for callers with an error of their own to
+// report or none to return.
+int sync_all(std::initializer_list<hipStream_t> order, bool quiet = false) {
+    for (hipStream_t q : order) {
+        if (!q) continue;
+        if (quiet) (void)hipStreamSynchronize(q);
+        else KARMA_HIP(hipStreamSynchronize(q));
+    }
+    return KARMA_OK;
+}
+
+// hipStreamWaitEvent, counted once (by KARMA_HIP)
+int wait_event(hipStream_t w, hipEvent_t ev) {
+    KARMA_HIP(hipStreamWaitEvent(w, ev, 0));
+    return KARMA_OK;
+}
+
 // The profile buffer grows only with both streams idle: the side stream may
 // still be writing the old one, and the allocator would hand it to a
 // main-stream allocation (it was allocated there) at once.
 int ensure_prof(karma_step* s, DevArray<double>& prof, size_t n) {
     if (prof.n >= n) return KARMA_OK;
-    KARMA_HIP(hipStreamSynchronize(s->side_s));
-    KARMA_HIP(hipStreamSynchronize(s->side_alt_s));
-    KARMA_HIP(hipStreamSynchronize(s->main_s));
-    KARMA_HIP(hipStreamSynchronize(s->alt_s));
+    KARMA_TRY(sync_all({s->side_s, s->side_alt_s, s->main_s, s->alt_s}));
     return prof.alloc(s->ctx, n);
 }
 template <typename T>
@@ -740,20 +754,28 @@ int drop_outputs(karma_step* s) {
     return bury(s, false);
 }
 
+// OR of every rank's presence bitmap.  All of a deferred step's column
+// exchange (every rank's store is ACGT-only, so there are no exception keys),
+// the first half of a synchronous step's.
+int exchange_presence(karma_step* s, karma_kmer_plan* plan, karma_comm* c) {
+    karma_ctx* ctx = s->ctx;
+    int64_t nw = 0;
+    KARMA_TRY(karma_kmer_presence_words(plan, &nw));
+    DevArray<uint32_t> words, all;
+    KARMA_TRY(words.alloc(ctx, nw));
+    KARMA_TRY(all.alloc(ctx, nw * s->world));
+    KARMA_TRY(karma_kmer_presence_get(plan, words.ptr));
+    KARMA_TRY(karma_comm_allgather(c, words.ptr, all.ptr, nw * 4));
+    return karma_kmer_presence_merge(plan, all.ptr, s->world);  // stream-ordered: words / all back to the cache
+}
+
 // The column set's exchange (kmer.py:146-179 is a global sorted union): OR of
 // every rank's presence bitmap, union of every rank's exception keys.  On the
 // side communicator, issued in the same order on every rank.
 int exchange_columns(karma_step* s, karma_kmer_plan* plan, karma_comm* c) {
     karma_ctx* ctx = s->ctx;
     const int W = s->world;
-    int64_t nw = 0;
-    KARMA_TRY(karma_kmer_presence_words(plan, &nw));
-    DevArray<uint32_t> words, all;
-    KARMA_TRY(words.alloc(ctx, nw));
-    KARMA_TRY(all.alloc(ctx, nw * W));
-    KARMA_TRY(karma_kmer_presence_get(plan, words.ptr));
-    KARMA_TRY(karma_comm_allgather(c, words.ptr, all.ptr, nw * 4));
-    KARMA_TRY(karma_kmer_presence_merge(plan, all.ptr, W));
+    KARMA_TRY(exchange_presence(s, plan, c));
     // exception keys: sizes, then one padded all-gather
     int64_t ne = 0;
     KARMA_TRY(karma_kmer_exceptions_count(plan, &ne));
@@ -780,20 +802,6 @@ int exchange_columns(karma_step* s, karma_kmer_plan* plan, karma_comm* c) {
         off += sizes[r];
     }
     return karma_kmer_exceptions_set(plan, keys.ptr, tot);  // sorts and dedups (stream-ordered)
-}
-
-// The presence bitmaps alone (a deferred step: every rank's store is ACGT-only,
-// so there are no exception keys to exchange).
-int exchange_presence(karma_step* s, karma_kmer_plan* plan, karma_comm* c) {
-    karma_ctx* ctx = s->ctx;
-    int64_t nw = 0;
-    KARMA_TRY(karma_kmer_presence_words(plan, &nw));
-    DevArray<uint32_t> words, all;
-    KARMA_TRY(words.alloc(ctx, nw));
-    KARMA_TRY(all.alloc(ctx, nw * s->world));
-    KARMA_TRY(karma_kmer_presence_get(plan, words.ptr));
-    KARMA_TRY(karma_comm_allgather(c, words.ptr, all.ptr, nw * 4));
-    return karma_kmer_presence_merge(plan, all.ptr, s->world);  // stream-ordered: words / all back to the cache
 }
 
 // The owners' readset totals, gathered from every owner's slice (in place for
@@ -829,11 +837,8 @@ int allgather_slices(karma_step* s, int64_t* buf) {
 // per purpose, created on first use)
 int stream_after(hipEvent_t* ev, hipStream_t on, hipStream_t w) {
     if (!*ev) KARMA_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    if (counted_call("hipEventRecord")) ++t_hip_calls;
     KARMA_HIP(hipEventRecord(*ev, on));
-    if (counted_call("hipStreamWaitEvent")) ++t_hip_calls;
-    KARMA_HIP(hipStreamWaitEvent(w, *ev, 0));
-    return KARMA_OK;
+    return wait_event(w, *ev);
 }
 
 // ---- the synchronous step ------------------------------------------------------
@@ -847,8 +852,7 @@ int run_sync(karma_step* s, karma_contigs* store, const uint32_t* rec, int64_t A
         // deferred steps' exchanges may still be queued on the exchange stream
         // (a re-run checked 3 steps back): the main stream's collectives and
         // the records job's reuse of their lists come after them
-        if (counted_call("hipStreamWaitEvent")) ++t_hip_calls;
-        KARMA_HIP(hipStreamWaitEvent(s->main_s, s->ev_tail[s->tail_last], 0));
+        KARMA_TRY(wait_event(s->main_s, s->ev_tail[s->tail_last]));
     }
     if (s->world > 1 && s->one_comm && !sequential) {
         // the column exchange below (side stream, the one communicator) after
@@ -964,13 +968,13 @@ int check_entry(karma_step* s, const karma_step::Pending& p, bool* slow) {
     // a step that runs again: its pair list may be incomplete (an overflowed
     // bucket or exchange slot), so the merge-order and zero-total words are
     // artifacts of the truncation; the re-run checks them on complete lists
-    const int64_t err = *slow ? st.err & ~int64_t(8 | 16) : st.err;
+    const int64_t err = *slow ? st.err & ~int64_t(kErrZeroTotal | kErrMergeOrder) : st.err;
     if (err) {
-        KARMA_CHECK(!(err & 1), KARMA_ERR_UNSORTED, "records are not grouped by read (read ids decrease)");
-        KARMA_CHECK(!(err & 2), KARMA_ERR_ARG, "a record's contig index is >= n_contigs (%lld)",
+        KARMA_CHECK(!(err & kErrOrder), KARMA_ERR_UNSORTED, "records are not grouped by read (read ids decrease)");
+        KARMA_CHECK(!(err & kErrRange), KARMA_ERR_ARG, "a record's contig index is >= n_contigs (%lld)",
                     (long long)s->n_glob);
-        KARMA_CHECK(!(err & 16), KARMA_ERR_UNSORTED, "karma_pairs_merge_runs: a run is not sorted by key");
-        KARMA_CHECK(!(err & 8), KARMA_ERR_ZERO_DIV, "division by zero: a shared count over a zero total");
+        KARMA_CHECK(!(err & kErrMergeOrder), KARMA_ERR_UNSORTED, "karma_pairs_merge_runs: a run is not sorted by key");
+        KARMA_CHECK(!(err & kErrZeroTotal), KARMA_ERR_ZERO_DIV, "division by zero: a shared count over a zero total");
         KARMA_CHECK(false, KARMA_ERR_STATE, "code partition: block counts disagree with the classify histogram");
     }
     return KARMA_OK;
@@ -1043,171 +1047,112 @@ int drain(karma_step* s, bool wait) {
     return KARMA_OK;
 }
 
-int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64_t A, bool flg, bool sequential) {
+// The streams of a deferred step's schedule (step_schedule.h), as run_deferred maps its roles.
+struct StepStreams {
+    hipStream_t records, side, tail, xs, fork;
+};
+
+using JobGuard = std::unique_ptr<SetsJob, void (*)(SetsJob*)>;
+
+// Phase 1, records stream: the records job up to its final kernel; no readback.
+int deferred_records(karma_step* s, const DeferredSchedule& sc, const StepStreams& q, karma_step::Tail& tl,
+                     const uint32_t* rec, int64_t A, bool flg, JobGuard& jg, SetsDeferred* v) {
     karma_ctx* ctx = s->ctx;
-    KARMA_TRY(drop_outputs(s));  // a deferred step has no outputs to read
-    ++s->n_deferred;
-    const uint64_t seq = ++s->seq;
-    // Two batches in flight pay off only while one batch leaves the chip idle
-    // between its short kernels: at config 3's size (308M records) two records
-    // jobs side by side took 1.89 ms per batch against 1.23 ms one after the
-    // other (they evict each other's partition runs from the caches); the
-    // 8-rank strong preview (38.6M records) went 0.237 -> 0.199 ms.
-    // several processes: two main streams only with the exchange stream
-    // (the main communicator's operations then all go to side_alt_s)
-    const bool two = (s->world == 1 || (s->xstream && !sequential)) &&
-                     (s->streams ? s->streams == 2 : A < kAltMaxRecords);
-    // the exchange stream carries the tail: with two main streams, and with
-    // one communicator also behind one main stream (it then holds every
-    // collective of the step, the presence all-gather included)
-    // (several processes only.  Emulated ranks keep the tail on the main
-    // stream: the exchange stream's 8 more event calls per step cost more than
-    // the overlap gains, 8-rank strong preview 0.200 / 0.204 against 0.193 /
-    // 0.186 ms, same box)
-    const bool xs_on = !sequential && s->xstream && s->world > 1 && (two || s->one_comm);
-    if (two) ++s->n_two;
-    if (xs_on) ++s->n_xs;
-    const int par = sequential || !two ? 0 : (int)(seq & 1);
-    hipStream_t const ms = par ? s->alt_s : s->main_s;
-    hipStream_t const xs = s->side_alt_s;
-    if (s->tail_set[par]) {
-        // the records job's lists (this main stream's cache) and tail[par]
-        // were last used on the exchange stream
-        if (counted_call("hipStreamWaitEvent")) ++t_hip_calls;
-        KARMA_HIP(hipStreamWaitEvent(ms, s->ev_tail[par], 0));
-    }
-    // One main stream (large batches): the records job does not wait for the
-    // previous batch's profile.  Joining them (classify then never shares HBM
-    // with a profile) measured config 3 at 1.29-1.31 against 1.16-1.21 ms per
-    // step (profiles/r04/measurements.md (ab_join)).
-    karma_step::Tail& tl = s->tail[par];
-    // A failure between here and the status kernel's launch leaves this job's
-    // flags, counters and block items in the tail's own control block (only
-    // the status kernel clears it), and the next job on this tail would take
-    // the block as zeroed (no probe, no memset): clear it once every stream is
-    // idle (a kernel of this step may still use it), and leave no newest
-    // deferred step without a status behind.
-    struct FailGuard {
-        karma_step* s;
-        karma_step::Tail& tl;
-        uint64_t seq;
-        bool armed = true;
-        ~FailGuard() {
-            if (!armed) return;
-            for (hipStream_t q : {s->side_s, s->side_alt_s, s->main_s, s->alt_s}) (void)hipStreamSynchronize(q);
-            if (tl.ctrl.ptr) {
-                (void)hipMemsetAsync(tl.ctrl.ptr, 0, tl.ctrl.n * 8, s->main_s);
-                (void)hipStreamSynchronize(s->main_s);
-            }
-            if (s->prof_seq == seq) {
-                s->prof_seq = 0;
-                s->prof_M = -1;
-            }
-        }
-    } fail{s, tl, seq};
-    StreamScope on_main(ctx, ms);
-    s->prof_seq = seq;
-    s->prof_par = par;
-    s->prof_M = -1;
+    StreamScope on_records(ctx, q.records);
     if (s->exchange) KARMA_TRY(karma_graph_split_hint(ctx, s->bounds.data(), s->nranks));
-    // records job (main stream) up to its final kernel; no readback
-    SetsJob* job = nullptr;
-    SetsDeferred v;
     SetsOpts jo;
-    // the general-read branch: on the idle spare main stream with one main
-    // stream; kept on the main stream with two (see side_alt_s)
-    jo.single_stream = two;
-    jo.fork = two ? nullptr : s->alt_s;
-    // where the side stream's profile may start (SetsJob::launch): with one main
-    // stream, after the code partition -- the profile's writes then share HBM
-    // with the LDS-bound code reduce and final kernel instead of the next
-    // batch's classify (config 3: 1.15 against 1.20-1.22 ms per step,
-    // profiles/r04/measurements.md (ab_mark3)); with two, after the final kernel
-    jo.mark = two ? kMarkTwo : flg ? kMarkOneFlagged : kMarkOne;
+    jo.single_stream = sc.single_stream;
+    jo.fork = q.fork;
+    jo.mark = sc.mark;
     jo.ctrl = tl.ctrl.ptr;  // zero: the last status kernel of this tail cleared it
     jo.ctrl_words = (int64_t)tl.ctrl.n;
     RecIn rin;
     if (flg) rin.fw = rec;
     else rin.pr = reinterpret_cast<const uint2*>(rec);
-    KARMA_TRY(sets_begin_deferred(ctx, rin, A, s->n_glob, jo, &job, &v));
-    std::unique_ptr<SetsJob, void (*)(SetsJob*)> jg(job, sets_release);
-    if (v.ctrl) ++s->n_own;
-    if (!v.ctrl) {
-        // the job needed a larger block than this tail's: grow it for the next
-        // job on this tail (with every stream idle: the old block may still
-        // be cleared by a status kernel), zeroed in stream order
-        KARMA_HIP(hipStreamSynchronize(s->side_s));
-        KARMA_HIP(hipStreamSynchronize(s->side_alt_s));
-        KARMA_HIP(hipStreamSynchronize(s->main_s));
-        KARMA_HIP(hipStreamSynchronize(s->alt_s));
-        KARMA_TRY(tl.ctrl.alloc(ctx, (size_t)(v.ctrl_need + v.ctrl_need / 4 + 64)));
-        KARMA_HIP(hipMemsetAsync(tl.ctrl.ptr, 0, tl.ctrl.n * 8, ms));
+    SetsJob* job = nullptr;
+    KARMA_TRY(sets_begin_deferred(ctx, rin, A, s->n_glob, jo, &job, v));
+    jg.reset(job);
+    if (v->ctrl) {
+        ++s->n_own;
+        return KARMA_OK;
     }
-    // side stream: presence, column table (M stays on the device), then the
-    // profile behind the graph's final kernel (sequential: all on the main
-    // stream, every kernel alone on the chip -- the per-kernel timing pass)
-    hipStream_t const side = sequential ? ms : (par && !xs_on ? s->side_alt_s : s->side_s);
-    int rc = KARMA_OK;
-    {
-        StreamScope on_side(ctx, side);
-        DevArray<uint32_t>& pz = s->plan_zero[side == s->side_alt_s ? 1 : 0];
-        PlanOpts po;
-        if (!sequential) {
-            // 2,048 + 2 words: the bitmap of every k <= 8 and the exception counter
-            if (!pz.ptr) {
-                KARMA_TRY(pz.alloc(ctx, 2048 + 2));
-                KARMA_HIP(hipMemsetAsync(pz.ptr, 0, pz.n * 4, side));
-            }
-            po.zeroed = pz.ptr;
-            po.zeroed_words = (int64_t)pz.n;
+    // the job needed a larger block than this tail's: grow it for the next
+    // job on this tail (with every stream idle: the old block may still
+    // be cleared by a status kernel), zeroed in stream order
+    KARMA_TRY(sync_all({s->side_s, s->side_alt_s, s->main_s, s->alt_s}));
+    KARMA_TRY(tl.ctrl.alloc(ctx, (size_t)(v->ctrl_need + v->ctrl_need / 4 + 64)));
+    KARMA_HIP(hipMemsetAsync(tl.ctrl.ptr, 0, tl.ctrl.n * 8, q.records));
+    return KARMA_OK;
+}
+
+// Phase 2, side stream: presence, column table (M stays on the device), then
+// the profile behind the records job's mark (sequential: all on the records
+// stream, every kernel alone on the chip -- the per-kernel timing pass).
+int deferred_profile(karma_step* s, const DeferredSchedule& sc, const StepStreams& q, karma_step::Tail& tl,
+                     karma_contigs* store, uint64_t seq, bool sequential) {
+    karma_ctx* ctx = s->ctx;
+    StreamScope on_side(ctx, q.side);
+    DevArray<uint32_t>& pz = s->plan_zero[sc.plan_zero];
+    PlanOpts po;
+    if (!sequential) {
+        // 2,048 + 2 words: the bitmap of every k <= 8 and the exception counter
+        if (!pz.ptr) {
+            KARMA_TRY(pz.alloc(ctx, 2048 + 2));
+            KARMA_HIP(hipMemsetAsync(pz.ptr, 0, pz.n * 4, q.side));
         }
-        karma_kmer_plan* plan = nullptr;
-        rc = kmer_plan_create(ctx, store, s->kmode, po, &plan);
-        if (!rc && s->world > 1) {
-            if (xs_on && s->one_comm) {
-                // the presence all-gather on the exchange stream (behind the previous
-                // batch's tail and a synchronous step's collectives), the column
-                // table back on the side stream behind it
-                rc = stream_after(&s->ev_pres, side, xs);
-                if (!rc && s->sync_set) {
-                    rc = stream_after(&s->ev_sync, s->main_s, xs);
-                    s->sync_set = false;
-                }
-                {
-                    StreamScope on_xs(ctx, xs);
-                    if (!rc) rc = exchange_presence(s, plan, s->comm);
-                    if (!rc) rc = stream_after(&s->ev_pres2, xs, side);
-                }
-            } else {
-                // sequential (one stream), or the side communicator on the side stream
-                rc = exchange_presence(s, plan, s->scomm ? s->scomm : s->comm);
-            }
-        }
-        // M: into the device ring (the profile reads it) and the mapped ring (the
-        // host reads it once the step is done); nothing on the main streams waits for it
-        int64_t* const m_dev = s->m_ring.ptr + seq % kRing;
-        if (!rc) rc = kmer_finalize_device(plan, m_dev, s->mring_d + seq % kRing);
-        // (a failed plan's block was not cleared by a column table)
-        if (rc && !sequential && pz.ptr) (void)hipMemsetAsync(pz.ptr, 0, pz.n * 4, side);
-        if (!rc) rc = ensure_prof(s, tl.prof, (size_t)std::max<int64_t>(1, s->n_loc * kmer_m_cap(plan)));
-        if (!rc && ctx->mark_set && !sequential) {
-            if (counted_call("hipStreamWaitEvent")) ++t_hip_calls;
-            rc = hipStreamWaitEvent(side, ctx->mark_ev, 0) == hipSuccess ? KARMA_OK : KARMA_ERR_HIP;
-        }
-        if (!rc && s->n_loc) rc = kmer_profile_device_m(plan, tl.prof.ptr, m_dev);
-        if (plan) karma_kmer_plan_destroy(plan);  // its buffers return to the side stream's cache
+        po.zeroed = pz.ptr;
+        po.zeroed_words = (int64_t)pz.n;
     }
-    KARMA_TRY(rc);
-    if (xs_on) {  // the tail on the exchange stream, behind this records job (and a synchronous step's collectives)
-        KARMA_TRY(stream_after(&s->ev_rec, ms, xs));
-        // (one communicator: the presence all-gather above already waited for them)
+    karma_kmer_plan* plan = nullptr;
+    int rc = kmer_plan_create(ctx, store, s->kmode, po, &plan);
+    if (!rc && s->world > 1) {
+        if (sc.xs_on && s->one_comm) {
+            // the presence all-gather on the exchange stream (behind the previous
+            // batch's tail and a synchronous step's collectives), the column
+            // table back on the side stream behind it
+            rc = stream_after(&s->ev_pres, q.side, q.xs);
+            if (!rc && s->sync_set) {
+                rc = stream_after(&s->ev_sync, s->main_s, q.xs);
+                s->sync_set = false;
+            }
+            {
+                StreamScope on_xs(ctx, q.xs);
+                if (!rc) rc = exchange_presence(s, plan, s->comm);
+                if (!rc) rc = stream_after(&s->ev_pres2, q.xs, q.side);
+            }
+        } else {
+            // sequential (one stream), or the side communicator on the side stream
+            rc = exchange_presence(s, plan, s->scomm ? s->scomm : s->comm);
+        }
+    }
+    // M: into the device ring (the profile reads it) and the mapped ring (the
+    // host reads it once the step is done); nothing on the main streams waits for it
+    int64_t* const m_dev = s->m_ring.ptr + seq % kRing;
+    if (!rc) rc = kmer_finalize_device(plan, m_dev, s->mring_d + seq % kRing);
+    // (a failed plan's block was not cleared by a column table)
+    if (rc && !sequential && pz.ptr) (void)hipMemsetAsync(pz.ptr, 0, pz.n * 4, q.side);
+    if (!rc) rc = ensure_prof(s, tl.prof, (size_t)std::max<int64_t>(1, s->n_loc * kmer_m_cap(plan)));
+    if (!rc && ctx->mark_set && !sequential) rc = wait_event(q.side, ctx->mark_ev);
+    if (!rc && s->n_loc) rc = kmer_profile_device_m(plan, tl.prof.ptr, m_dev);
+    if (plan) karma_kmer_plan_destroy(plan);  // its buffers return to the side stream's cache
+    return rc;
+}
+
+// Phase 3, tail stream: the exchange (several ranks), the owner's merge, the
+// edge stage around the totals all-gather and the status kernel, all sized
+// on the device.
+int deferred_tail(karma_step* s, const DeferredSchedule& sc, const StepStreams& q, karma_step::Tail& tl,
+                  const SetsDeferred& v, uint64_t seq) {
+    karma_ctx* ctx = s->ctx;
+    if (sc.xs_on) {  // behind this records job (and a synchronous step's collectives)
+        KARMA_TRY(stream_after(&s->ev_rec, q.records, q.xs));
+        // (one communicator: the presence all-gather already waited for them)
         if (s->sync_set) {
-            KARMA_TRY(stream_after(&s->ev_sync, s->main_s, xs));
+            KARMA_TRY(stream_after(&s->ev_sync, s->main_s, q.xs));
             s->sync_set = false;
         }
     }
-    StreamScope on_tail(ctx, xs_on ? xs : ms);
-    // main stream: the tail, sized on the device
+    StreamScope on_tail(ctx, q.tail);
     const uint64_t* lk = v.keys;
     const int64_t* lc = v.counts;
     const int64_t* n_dev = v.dst + v.B;
@@ -1285,13 +1230,71 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
                 (unsigned long long)seq);
     KARMA_LAUNCH(ctx, "step_status", step_status_kernel, 1, 256, 0, v.flags, v.counters, v.ovf, v.B, v.dst, mbad,
                  tl.est.ptr, s->ring_d + seq % kRing, seq, v.ctrl, v.ctrl ? v.ctrl_need : (int64_t)0);
-    if (xs_on) {
-        if (!s->ev_tail[par]) KARMA_HIP(hipEventCreateWithFlags(&s->ev_tail[par], hipEventDisableTiming));
-        if (counted_call("hipEventRecord")) ++t_hip_calls;
-        KARMA_HIP(hipEventRecord(s->ev_tail[par], xs));
-        s->tail_set[par] = true;
-        s->tail_last = par;
+    if (sc.xs_on) {
+        // the records job's lists and this tail's buffers return to their main
+        // stream behind this event (run_deferred, run_sync)
+        if (!s->ev_tail[sc.par]) KARMA_HIP(hipEventCreateWithFlags(&s->ev_tail[sc.par], hipEventDisableTiming));
+        KARMA_HIP(hipEventRecord(s->ev_tail[sc.par], q.xs));
+        s->tail_set[sc.par] = true;
+        s->tail_last = sc.par;
     }
+    return KARMA_OK;
+}
+
+// A failure between a deferred step's records job and its status kernel's
+// launch leaves the job's flags, counters and block items in the tail's own
+// control block (only the status kernel clears it), and the next job on this
+// tail would take the block as zeroed (no probe, no memset): clear it once
+// every stream is idle (a kernel of this step may still use it), and leave no
+// newest deferred step without a status behind.
+struct FailGuard {
+    karma_step* s;
+    karma_step::Tail& tl;
+    uint64_t seq;
+    bool armed = true;
+    ~FailGuard() {
+        if (!armed) return;
+        (void)sync_all({s->side_s, s->side_alt_s, s->main_s, s->alt_s}, true);
+        if (tl.ctrl.ptr) {
+            (void)hipMemsetAsync(tl.ctrl.ptr, 0, tl.ctrl.n * 8, s->main_s);
+            (void)hipStreamSynchronize(s->main_s);
+        }
+        if (s->prof_seq == seq) {
+            s->prof_seq = 0;
+            s->prof_M = -1;
+        }
+    }
+};
+
+int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64_t A, bool flg, bool sequential) {
+    KARMA_TRY(drop_outputs(s));  // a deferred step has no outputs to read
+    ++s->n_deferred;
+    const uint64_t seq = ++s->seq;
+    const DeferredSchedule sc =
+        deferred_schedule({s->world, s->xstream, s->one_comm, s->streams, A, sequential, flg, seq});
+    // the one place roles become streams
+    hipStream_t const by_role[] = {nullptr, s->main_s, s->alt_s, s->side_s, s->side_alt_s};
+    auto on = [&](StreamRole r) { return by_role[(int)r]; };
+    const StepStreams q{on(sc.records), on(sc.side), on(sc.tail), on(kExchangeStream), on(sc.fork)};
+    if (sc.two) ++s->n_two;
+    if (sc.xs_on) ++s->n_xs;
+    // the records job's lists (this main stream's cache) and tail[par] were
+    // last used on the exchange stream
+    if (s->tail_set[sc.par]) KARMA_TRY(wait_event(q.records, s->ev_tail[sc.par]));
+    // One main stream (large batches): the records job does not wait for the
+    // previous batch's profile.  Joining them (classify then never shares HBM
+    // with a profile) measured config 3 at 1.29-1.31 against 1.16-1.21 ms per
+    // step (profiles/r04/measurements.md (ab_join)).
+    karma_step::Tail& tl = s->tail[sc.par];
+    FailGuard fail{s, tl, seq};  // every return below passes through it
+    s->prof_seq = seq;
+    s->prof_par = sc.par;
+    s->prof_M = -1;
+    JobGuard job(nullptr, sets_release);  // released (stream-ordered) once the tail is enqueued
+    SetsDeferred v;
+    KARMA_TRY(deferred_records(s, sc, q, tl, rec, A, flg, job, &v));
+    KARMA_TRY(deferred_profile(s, sc, q, tl, store, seq, sequential));
+    KARMA_TRY(deferred_tail(s, sc, q, tl, v, seq));
     fail.armed = false;
     s->pending.push_back({seq, store, rec, A, flg});
     return KARMA_OK;
@@ -1437,10 +1440,7 @@ int karma_step_sync(karma_step* s) {
         StreamScope on_main(ctx, s->main_s);
         KARMA_TRY(drain(s, true));
     }
-    KARMA_HIP(hipStreamSynchronize(s->side_s));
-    KARMA_HIP(hipStreamSynchronize(s->side_alt_s));
-    KARMA_HIP(hipStreamSynchronize(s->alt_s));
-    KARMA_HIP(hipStreamSynchronize(s->main_s));
+    KARMA_TRY(sync_all({s->side_s, s->side_alt_s, s->alt_s, s->main_s}));
     KARMA_TRY(bury(s, true));
     if (s->prof_seq) {  // every stream is idle: the newest deferred step's column count has landed
         s->prof_M = __atomic_load_n(&s->mring_h[s->prof_seq % kRing], __ATOMIC_ACQUIRE);
@@ -1537,10 +1537,7 @@ int karma_step_newest_edges(karma_step* s, uint32_t* a, uint32_t* b, int64_t* sh
 int karma_step_destroy(karma_step* s) {
     if (!s) return KARMA_OK;
     hipSetDevice(s->ctx->device);
-    if (s->main_s) hipStreamSynchronize(s->main_s);
-    if (s->alt_s) hipStreamSynchronize(s->alt_s);
-    if (s->side_s) hipStreamSynchronize(s->side_s);
-    if (s->side_alt_s) hipStreamSynchronize(s->side_alt_s);
+    (void)sync_all({s->main_s, s->alt_s, s->side_s, s->side_alt_s}, true);
     s->pending.clear();
     s->E = 0;  // outputs dropped unread
     drop_outputs(s);
