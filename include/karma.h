@@ -257,6 +257,10 @@ int karma_graph_records_end(karma_graph_job* job, karma_pairs** out);
  * bounds then answers without a launch or a synchronisation.  Applies to one
  * job; at most 64 ranks. */
 int karma_graph_split_hint(karma_ctx* ctx, const int64_t* bounds, int nranks);
+/* For tests: the resident blocks per compute unit (the occupancy query, with
+ * the job's dynamic LDS) of the classify kernel a records job of n_contigs in
+ * rec_format (KARMA_REC_SORTED or KARMA_REC_FLAGGED) would launch. */
+int karma_graph_classify_occupancy(karma_ctx* ctx, int64_t n_contigs, int rec_format, int* blocks_per_cu);
 /* Salmon eq classes (read_graph.py:75-114): cls_off[n_classes+1] into members
  * (contig indices as listed, duplicates kept), counts[n_classes], pair_skip[c]=1
  * when the eq_size token is "1" (read_graph.py:102).  Totals (read_graph.py:86-92)

@@ -113,6 +113,7 @@ _SIGS = {
     "karma_graph_records_begin": [_c_p, _c_p, _i64, _i64, _i32, _i32, _PP],
     "karma_graph_records_end": [_c_p, _PP],
     "karma_graph_split_hint": [_c_p, _c_p, _i32],
+    "karma_graph_classify_occupancy": [_c_p, _i64, _i32, ctypes.POINTER(ctypes.c_int)],
     "karma_graph_eq": [_c_p, _c_p, _c_p, _c_p, _c_p, _i64, _i64, _i32, _PP],
     "karma_graph_eq_compact": [_c_p, _c_p, _c_p, _i64, _c_p, _i64, _i64, _PP],
     "karma_pairs_merge": [_c_p, _c_p, _c_p, _i64, _i32, _PP],

@@ -261,12 +261,10 @@ __device__ __forceinline__ uint32_t dpp_shr1(uint32_t old, uint32_t v) {  // lan
 // loop (a second walk inside the loop spilled 158 SGPRs: 222M -> 183M VALU)
 constexpr int kRareMax = int(kCChunk / kCIter);  // steps per chunk
 constexpr int kRareW = 5;                        // words per listed step
-// the one remaining compile-time variant: faster by instruction count (2 % fewer
-// VALU), not made the default on two calls' evidence; to be re-measured
-#ifndef KARMA_CLS_PACKED
-#define KARMA_CLS_PACKED 0  // binned flagged walk: own reads staged as (fm3 << 8 | 8-bit window), coded in bin_stage
-#endif
-constexpr int kCls2Waves = 4;  // 4: 0.541 ms; 5 (84 VGPRs): 0.545; 6 (80 VGPRs, 7 spilled): 0.576
+constexpr int kCls2Waves = 4;  // pairs records, round 1: 4: 0.541 ms; 5 (84 VGPRs): 0.545; 6 (80 VGPRs, 7 spilled): 0.576
+// the binned classify on flagged records fits 5 blocks per CU up to 49 code
+// buckets (its LDS; 73 VGPRs): 3 blocks 0.40 ms, 4 0.34
+constexpr int kCls2BinWaves = 5;
 
 // ---- binned classify (BIN): compact codes straight into bucket runs --------------
 // With few code buckets (Bc <= kBinMaxBc: n_contigs <= 229,376 at bwc = 12)
@@ -283,7 +281,7 @@ constexpr int kCls2Waves = 4;  // 4: 0.541 ms; 5 (84 VGPRs): 0.545; 6 (80 VGPRs,
 // the u32 code stream, the partition kernel and its u16 runs (1.2 GB of
 // intermediate traffic at config 3) are gone.
 constexpr int kBinQ = 64;        // codes per queue and per back segment (128 B)
-constexpr int kBinMaxBc = 56;    // code buckets with a queue (LDS: 56 x 128 B per wave; 7 nibble words)
+constexpr int kBinMaxBc = 56;    // code buckets with a queue (LDS: 128 B per bucket and wave; 7 nibble words)
 // header (4 x uint4 per chunk): x0..x6 granule nibbles of buckets 0..55, x7
 // back count, x8-x9 back mask, x10-x13 directory bytes 0..15, x14 codes
 constexpr int kBinHdr = 4;
@@ -304,7 +302,8 @@ struct BinArgs {
 // 512-record step is 2 KB (two 16-byte units per lane), no read ids to
 // compare or order-check
 template <bool HIST, bool COMPACT, bool REMAP = false, bool BIN = false, bool FLAG = false>
-__global__ void __launch_bounds__(kCW) __attribute__((amdgpu_waves_per_eu(kCls2Waves, kCls2Waves)))
+__global__ void __launch_bounds__(kCW)
+    __attribute__((amdgpu_waves_per_eu(kCls2Waves, BIN && FLAG ? kCls2BinWaves : kCls2Waves)))
 classify2_kernel(ClassArgs P, BinArgs Q) {
     static_assert(!(HIST && BIN), "the binned classify has no partition block histograms");
     // P's fields only the rare steps' replay uses (after the chunk's loop),
@@ -337,7 +336,9 @@ classify2_kernel(ClassArgs P, BinArgs Q) {
     // fm3 + 6]), one shift-or per record; bin_stage turns 64 of them at a time
     // into codes and lists the step when one is not compact.  fm3 keeps 24
     // bits there, so the range guard lists steps with any contig >= 2^24
-    constexpr bool PK = RC && KARMA_CLS_PACKED;
+    // (classify alone 0.3265 -> 0.321 ms at config 3 once the profile's
+    // dispatch order is pinned)
+    constexpr bool PK = RC;
     constexpr uint32_t kWinTop = PK ? 7u : 31u;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -356,17 +357,22 @@ classify2_kernel(ClassArgs P, BinArgs Q) {
     // unit index XOR-ed with (l >> 2) & 3: conflict-free for the 16-byte stores
     // (8-lane groups, banks mod 32) and for the row reads (16-lane groups,
     // banks mod 64) alike.  BIN: half of it (rows of lanes 0-31, then of lanes
-    // 32-63), to leave LDS for the bucket queues at 4 blocks per CU.
-    constexpr int kRows = BIN ? 32 : 64;
+    // 32-63), to leave LDS for the bucket queues at 4 blocks per CU.  BIN on
+    // flagged records: a quarter (1 KB: the rows of 16 lanes at a time, four
+    // passes; 256 staged codes), so that with the queues sized by the job's Bc
+    // a wave's LDS stays within 8 KB up to 49 code buckets: 5 blocks per CU.
+    constexpr int kRows = BIN ? (FLAG ? 16 : 32) : 64;
     __shared__ __attribute__((aligned(16))) u32x4 tbuf[kCW / 64][kRows * 4];
     u32x4* tb = tbuf[wave];
     // the chunk's codes per code bucket, added to its partition block's row at the end
     __shared__ uint32_t whist[kCW / 64][HIST ? kMaxBc : 1];
     uint32_t* wh = whist[wave];
     // BIN: the bucket queues, their fill counts, and rank -> bucket of the end flush
-    __shared__ __attribute__((aligned(16))) uint16_t bq[kCW / 64][BIN ? kBinMaxBc * kBinQ : 8];
+    // (the queues are the launch's dynamic LDS, P.Bc x kBinQ codes per wave:
+    // class_bin_lds; the counts stay sized for kBinMaxBc)
+    extern __shared__ __attribute__((aligned(16))) uint16_t cls_bq[];
     __shared__ uint32_t bcnt[kCW / 64][BIN ? kBinMaxBc : 1];
-    uint16_t* const q = bq[wave];
+    uint16_t* const q = cls_bq + (BIN ? wave * P.Bc * kBinQ : 0);
     uint32_t* const qn = bcnt[wave];
     // back-segment bookkeeping, touched only when a queue fills (kept in LDS,
     // not in registers across the walk): [0] back count, [1..2] back mask,
@@ -435,11 +441,17 @@ classify2_kernel(ClassArgs P, BinArgs Q) {
         }
     };
     // BIN: a step's codes are staged (ballot-compacted u32) in the transpose
-    // buffer, idle during the walk (a step ends <= 512 reads: 2 KB), and go
-    // into the queues once per step, 64 at a time, instead of at each of the
-    // walk's 8 emit points
+    // buffer, idle during the walk, and go into the queues 64 at a time, once
+    // per step (8 records per lane: a step ends <= 512 reads, 2 KB) or after
+    // every four emit points (16 per lane), instead of at each emit point
     uint32_t* const stg = reinterpret_cast<uint32_t*>(tb);
     const uint32_t* const stg_l = stg + lane;
+    // codes the buffer holds, and the walk's emit points (<= 64 codes each)
+    // between two calls of bin_stage: the RPL - 1 own-read points and the
+    // merged read's make RPL, in groups of kStgPts
+    constexpr int kStgCap = kRows * 16;
+    constexpr int kStgPts = kStgCap / 64;
+    static_assert(!BIN || (kStgPts >= 1 && RPL % kStgPts == 0), "the staged codes of kStgPts emit points fit");
     uint32_t ns = 0;  // staged codes (uniform)
     uint32_t nc = 0, ng = 0;  // the chunk's codes and general reads
     // one value per lane of `b` into the staging area
@@ -455,7 +467,7 @@ classify2_kernel(ClassArgs P, BinArgs Q) {
         if (!ns) return;
         wave_lds_order();
         for (uint32_t j0 = 0; j0 < ns; j0 += 64) {
-            // unpredicated read (ns <= 512 codes: the 2 KB buffer; j0 + lane < 512 always; past ns masked off)
+            // unpredicated read (ns <= kStgCap codes, a multiple of 64: j0 + lane < kStgCap always; past ns masked off)
             uint32_t cd = stg_l[j0];
             uint64_t m = lanes((uint32_t)lane < ns - j0);
             if (PK) {
@@ -554,16 +566,20 @@ classify2_kernel(ClassArgs P, BinArgs Q) {
             // granule g at slot g ^ ((g >> 4) & 3): the stores' 8-lane groups
             // stay in one 16-granule row (a permutation of it), and the reads'
             // 16-lane groups (granules 4j + k) fall on 16 distinct bank quads
-            const int rl = lane & 31;
+            // (BIN: four passes of 64 granules, 1 KB: pass h holds unit h = the
+            // records of lanes 16h .. 16h + 15; the same slots and bank quads)
+            constexpr int kPass = BIN ? 4 : 2, kUP = kFPer / kPass, kPL = 64 / kPass;
+            static_assert(kFPer == 4 && kUP * 64 <= kRows * 4, "a pass fits the transpose buffer");
+            const int rl = lane & (kPL - 1);
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
+            for (int h = 0; h < kPass; ++h) {
 #pragma unroll
-                for (int u = 0; u < 2; ++u) {
+                for (int u = 0; u < kUP; ++u) {
                     const int g = 64 * u + lane;
-                    tb[g ^ ((g >> 4) & 3)] = buf[2 * h + u];
+                    tb[g ^ ((g >> 4) & 3)] = buf[kUP * h + u];
                 }
                 wave_sync();
-                if ((lane >> 5) == h) {
+                if (lane / kPL == h) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const int g = 4 * rl + k;
@@ -729,10 +745,10 @@ classify2_kernel(ClassArgs P, BinArgs Q) {
             uint64_t Si = S0;
 #pragma unroll
             for (int i = 0; i < RPL; ++i) {
-                // 16 records per lane: <= 64 codes per emit point, 16 of them --
-                // the first eight's codes go into the queues mid-walk (the staging
-                // buffer holds 512)
-                if (!RARE && BIN && i == 8) bin_stage();
+                // 16 records per lane: <= 64 codes per emit point, 16 of them
+                // (every record its own read: 64 at each) -- the codes of every
+                // four go into the queues mid-walk (the staging buffer holds kStgCap)
+                if (!RARE && BIN && i > 0 && i % kStgPts == 0) bin_stage();
                 if (i > 0) {
                     const uint64_t cap = Si & ~started;  // the first start: the head ends here
                     hd.win = in_mask(cap) ? st.win : hd.win;
@@ -1019,7 +1035,9 @@ classify2_kernel(ClassArgs P, BinArgs Q) {
         const uint32_t incl = wave_scan_incl(g), excl = incl - g;
         const uint32_t G = lane63(incl);
         uint16_t* const gt = reinterpret_cast<uint16_t*>(tb);  // <= 56 x 8 entries
-        uint8_t* const gb = reinterpret_cast<uint8_t*>(tb) + 1024;  // granule count per bucket
+        // granule count per bucket, behind the table (64 bytes: every lane writes its own)
+        static_assert(kBinMaxBc * 8 * 2 + 64 <= kRows * 64, "the flush's tables fit the transpose buffer");
+        uint8_t* const gb = reinterpret_cast<uint8_t*>(tb) + kBinMaxBc * 8 * 2;
         for (uint32_t i = 0; i < g; ++i) gt[excl + i] = (uint16_t)(lane << 3 | i);
         gb[lane] = (uint8_t)g;
         wave_lds_order();
@@ -2725,10 +2743,30 @@ int mark_at(int asked) {
     }();
     return env >= 0 ? env : asked >= 0 ? asked : kMarkAt;
 }
+// the binned classify's dynamic LDS: per wave, one queue of kBinQ u16 codes per code bucket
+size_t class_bin_lds(int Bc) { return (size_t)(kCW / 64) * (size_t)Bc * kBinQ * sizeof(uint16_t); }
 // a run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{})
 template <typename F>
 int pick(bool b, F f) {
     return b ? f(std::true_type{}) : f(std::false_type{});
+}
+// the binned classify (no code partition) while the code buckets' queues fit
+// its LDS; KARMA_BIN=0 in the environment keeps the partition (A/B)
+bool class_binned(int Bc) { return Bc > 0 && Bc < kAppendMinBc && Bc <= kBinMaxBc && bin_on(); }
+// f(kernel) with a job's classify instantiation:
+// classify2_kernel<HIST (append), COMPACT, REMAP (relabelled), BIN, FLAG (flagged records)>
+template <typename F>
+int with_classify(bool flagged, bool append, bool bin, bool relabeled, F f) {
+    return pick(flagged, [&](auto fl) -> int {
+        auto go = [&](auto ap, auto bn) -> int {
+            return pick(relabeled, [&](auto rl) -> int {
+                return f(&classify2_kernel<decltype(ap)::value, true, decltype(rl)::value, decltype(bn)::value,
+                                           decltype(fl)::value>);
+            });
+        };
+        return bin ? go(std::false_type{}, std::true_type{})
+                   : append ? go(std::true_type{}, std::false_type{}) : go(std::false_type{}, std::false_type{});
+    });
 }
 struct SetsJob {
     karma_ctx* ctx = nullptr;
@@ -2857,9 +2895,7 @@ int SetsJob::setup() {
     max_cflush = n_pblk + ceil_div(A, CodeStream::kCap) + 1;
     ccap = A + max_cflush * (8 * (int64_t)g.Bc + 8);
     if (append) KARMA_TRY(blk_hist.alloc(ctx, n_pblk * g.Bc));
-    // the binned classify (no code partition) while the code buckets' queues
-    // fit its LDS; KARMA_BIN=0 in the environment keeps the partition (A/B)
-    bin = !append && g.Bc > 0 && g.Bc <= kBinMaxBc && bin_on();
+    bin = class_binned(g.Bc);
     if (bin) {
         dir_cap = (int)(chunk / kBinQ);
         seg_cap = (uint32_t)(dir_cap + g.Bc);
@@ -2940,6 +2976,11 @@ int SetsJob::launch() {
         if (!ctx->mark_ev) KARMA_HIP(hipEventCreateWithFlags(&ctx->mark_ev, hipEventDisableTiming));
         KARMA_HIP(hipEventRecord(ctx->mark_ev, ctx->stream));
         ctx->mark_set = true;
+        if (opts.at_mark) {  // the caller's side-stream work, enqueued ahead of this job's next kernel
+            hipEvent_t passed = nullptr;
+            KARMA_TRY(opts.at_mark(opts.at_mark_arg, &passed));
+            if (passed) KARMA_HIP(hipStreamWaitEvent(ctx->stream, passed, 0));
+        }
         return KARMA_OK;
     };
     if (!relabeled) KARMA_TRY(mark(3));  // side-stream work may start beside classify
@@ -2956,19 +2997,9 @@ int SetsJob::launch() {
             C.c0 = c_from;
             const int64_t cg = ceil_div(c_to - c_from, kCW / 64);
             if (cg <= 0) return KARMA_OK;
-            // classify2_kernel<HIST (append), COMPACT, REMAP (relabelled), BIN, FLAG (flagged records)>
-            return pick(rec.flagged(), [&](auto fl) -> int {
-                auto go = [&](auto ap, auto bn) -> int {
-                    return pick(relabeled, [&](auto rl) -> int {
-                        KARMA_LAUNCH(ctx, "graph_classify",
-                                     (classify2_kernel<decltype(ap)::value, true, decltype(rl)::value,
-                                                       decltype(bn)::value, decltype(fl)::value>),
-                                     cg, kCW, 0, C, Bn);
-                        return KARMA_OK;
-                    });
-                };
-                return bin ? go(std::false_type{}, std::true_type{})
-                           : append ? go(std::true_type{}, std::false_type{}) : go(std::false_type{}, std::false_type{});
+            return with_classify(rec.flagged(), append, bin, relabeled, [&](auto kern) -> int {
+                KARMA_LAUNCH(ctx, "graph_classify", kern, cg, kCW, bin ? class_bin_lds(g.Bc) : 0, C, Bn);
+                return KARMA_OK;
             });
         };
         if (probe) {
@@ -3310,3 +3341,20 @@ int records_to_pairs_sets(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, karma
 }
 
 }  // namespace karma
+
+extern "C" int karma_graph_classify_occupancy(karma_ctx* ctx, int64_t n_contigs, int rec_format,
+                                              int* blocks_per_cu) {
+    using namespace karma;
+    KARMA_CHECK(ctx && blocks_per_cu && n_contigs >= 1 && n_contigs <= kMaxCompactN, KARMA_ERR_ARG,
+                "karma_graph_classify_occupancy: bad arguments (n_contigs %lld)", (long long)n_contigs);
+    KARMA_TRY(ctx_begin(ctx));
+    Geo g{};
+    KARMA_TRY(make_geo(n_contigs, &g));
+    const bool bin = class_binned(g.Bc);
+    const size_t lds = bin ? class_bin_lds(g.Bc) : 0;
+    return with_classify(rec_format == KARMA_REC_FLAGGED, g.Bc >= kAppendMinBc, bin, false, [&](auto kern) -> int {
+        KARMA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, reinterpret_cast<const void*>(kern),
+                                                               kCW, lds));
+        return KARMA_OK;
+    });
+}

@@ -298,6 +298,17 @@ struct SetsOpts {
     // launch ahead of classify, no relabel probe (classify votes)
     int64_t* ctrl = nullptr;
     int64_t ctrl_words = 0;
+    // Called once, on the host, right after the job has recorded ctx->mark_ev
+    // (first launch only): the caller enqueues there the side-stream work that
+    // waits for the mark, so it reaches the GPU ahead of the job's later
+    // kernels.  An event it hands back in *passed (recorded on the side stream
+    // behind its wait for the mark) is waited for by the job's stream before
+    // its next kernel: that kernel becomes ready only once the side stream is
+    // past the mark, so of two kernels ready at the same moment on two queues
+    // the side stream's goes first.  Plain event waits: nothing spins when the
+    // side-stream work is never launched.
+    int (*at_mark)(void* arg, hipEvent_t* passed) = nullptr;
+    void* at_mark_arg = nullptr;
 };
 // The same in two halves: sets_begin enqueues every kernel up to the control
 // block readback and returns; sets_end synchronises and assembles the list.

@@ -663,6 +663,10 @@ struct karma_step {
     // beside the main communicator's operations (round 4's mode).
     bool one_comm = true;
     hipEvent_t ev_pres = nullptr, ev_pres2 = nullptr, ev_pre = nullptr;
+    // recorded on the side stream between its wait for the records job's mark
+    // and the profile's launch; the records stream waits for it ahead of the
+    // final kernel (DeferredSchedule::profile_at_mark)
+    hipEvent_t ev_passed = nullptr;
     // deferred steps by mode (karma_step_info): two main streams, tail on the exchange stream
     int64_t n_two = 0, n_xs = 0, n_own = 0;  // ... and records jobs on the step's own control block
     int stall_s = 120;             // KARMA_STEP_STALL_S: a deferred status this late is KARMA_ERR_STALL
@@ -833,11 +837,15 @@ int allgather_slices(karma_step* s, int64_t* buf) {
     return KARMA_OK;
 }
 
-// stream `w` waits for everything recorded so far on stream `on` (one event
-// per purpose, created on first use)
-int stream_after(hipEvent_t* ev, hipStream_t on, hipStream_t w) {
+// one event per purpose, created on first use
+int record_event(hipEvent_t* ev, hipStream_t on) {
     if (!*ev) KARMA_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
     KARMA_HIP(hipEventRecord(*ev, on));
+    return KARMA_OK;
+}
+// stream `w` waits for everything recorded so far on stream `on`
+int stream_after(hipEvent_t* ev, hipStream_t on, hipStream_t w) {
+    KARMA_TRY(record_event(ev, on));
     return wait_event(w, *ev);
 }
 
@@ -1054,9 +1062,24 @@ struct StepStreams {
 
 using JobGuard = std::unique_ptr<SetsJob, void (*)(SetsJob*)>;
 
+// The profile phase as the records job's mark hook (SetsOpts::at_mark): what
+// deferred_profile needs, and whether the job called it (a job whose mark
+// position never comes -- KARMA_MARK_AT=0 -- leaves it to run_deferred).
+struct ProfileAtMark {
+    karma_step* s;
+    const DeferredSchedule* sc;
+    const StepStreams* q;
+    karma_step::Tail* tl;
+    karma_contigs* store;
+    uint64_t seq;
+    bool done = false;
+};
+int profile_at_mark(void* arg, hipEvent_t* passed);
+
 // Phase 1, records stream: the records job up to its final kernel; no readback.
+// hook: the profile phase, enqueued from inside the job at its mark (null: by run_deferred afterwards)
 int deferred_records(karma_step* s, const DeferredSchedule& sc, const StepStreams& q, karma_step::Tail& tl,
-                     const uint32_t* rec, int64_t A, bool flg, JobGuard& jg, SetsDeferred* v) {
+                     const uint32_t* rec, int64_t A, bool flg, JobGuard& jg, SetsDeferred* v, ProfileAtMark* hook) {
     karma_ctx* ctx = s->ctx;
     StreamScope on_records(ctx, q.records);
     if (s->exchange) KARMA_TRY(karma_graph_split_hint(ctx, s->bounds.data(), s->nranks));
@@ -1066,6 +1089,10 @@ int deferred_records(karma_step* s, const DeferredSchedule& sc, const StepStream
     jo.mark = sc.mark;
     jo.ctrl = tl.ctrl.ptr;  // zero: the last status kernel of this tail cleared it
     jo.ctrl_words = (int64_t)tl.ctrl.n;
+    if (hook) {
+        jo.at_mark = profile_at_mark;
+        jo.at_mark_arg = hook;
+    }
     RecIn rin;
     if (flg) rin.fw = rec;
     else rin.pr = reinterpret_cast<const uint2*>(rec);
@@ -1088,8 +1115,10 @@ int deferred_records(karma_step* s, const DeferredSchedule& sc, const StepStream
 // Phase 2, side stream: presence, column table (M stays on the device), then
 // the profile behind the records job's mark (sequential: all on the records
 // stream, every kernel alone on the chip -- the per-kernel timing pass).
+// passed (the mark hook): takes the event recorded on the side stream behind its
+// wait for the mark, ahead of the profile's launch
 int deferred_profile(karma_step* s, const DeferredSchedule& sc, const StepStreams& q, karma_step::Tail& tl,
-                     karma_contigs* store, uint64_t seq, bool sequential) {
+                     karma_contigs* store, uint64_t seq, bool sequential, hipEvent_t* passed = nullptr) {
     karma_ctx* ctx = s->ctx;
     StreamScope on_side(ctx, q.side);
     DevArray<uint32_t>& pz = s->plan_zero[sc.plan_zero];
@@ -1132,10 +1161,20 @@ int deferred_profile(karma_step* s, const DeferredSchedule& sc, const StepStream
     // (a failed plan's block was not cleared by a column table)
     if (rc && !sequential && pz.ptr) (void)hipMemsetAsync(pz.ptr, 0, pz.n * 4, q.side);
     if (!rc) rc = ensure_prof(s, tl.prof, (size_t)std::max<int64_t>(1, s->n_loc * kmer_m_cap(plan)));
-    if (!rc && ctx->mark_set && !sequential) rc = wait_event(q.side, ctx->mark_ev);
+    if (!rc && ctx->mark_set && !sequential) {
+        rc = wait_event(q.side, ctx->mark_ev);
+        if (!rc && passed) rc = record_event(&s->ev_passed, q.side);
+        if (!rc && passed) *passed = s->ev_passed;
+    }
     if (!rc && s->n_loc) rc = kmer_profile_device_m(plan, tl.prof.ptr, m_dev);
     if (plan) karma_kmer_plan_destroy(plan);  // its buffers return to the side stream's cache
     return rc;
+}
+
+int profile_at_mark(void* arg, hipEvent_t* passed) {
+    ProfileAtMark* const h = static_cast<ProfileAtMark*>(arg);
+    h->done = true;
+    return deferred_profile(h->s, *h->sc, *h->q, *h->tl, h->store, h->seq, false, passed);
 }
 
 // Phase 3, tail stream: the exchange (several ranks), the owner's merge, the
@@ -1292,8 +1331,9 @@ int run_deferred(karma_step* s, karma_contigs* store, const uint32_t* rec, int64
     s->prof_M = -1;
     JobGuard job(nullptr, sets_release);  // released (stream-ordered) once the tail is enqueued
     SetsDeferred v;
-    KARMA_TRY(deferred_records(s, sc, q, tl, rec, A, flg, job, &v));
-    KARMA_TRY(deferred_profile(s, sc, q, tl, store, seq, sequential));
+    ProfileAtMark hook{s, &sc, &q, &tl, store, seq};
+    KARMA_TRY(deferred_records(s, sc, q, tl, rec, A, flg, job, &v, sc.profile_at_mark ? &hook : nullptr));
+    if (!hook.done) KARMA_TRY(deferred_profile(s, sc, q, tl, store, seq, sequential));
     KARMA_TRY(deferred_tail(s, sc, q, tl, v, seq));
     fail.armed = false;
     s->pending.push_back({seq, store, rec, A, flg});
@@ -1544,7 +1584,8 @@ int karma_step_destroy(karma_step* s) {
     bury(s, true);
     for (auto& ev : s->grave_ev)
         if (ev) hipEventDestroy(ev);
-    for (hipEvent_t ev : {s->ev_rec, s->ev_sync, s->ev_tail[0], s->ev_tail[1], s->ev_pres, s->ev_pres2, s->ev_pre})
+    for (hipEvent_t ev : {s->ev_rec, s->ev_sync, s->ev_tail[0], s->ev_tail[1], s->ev_pres, s->ev_pres2, s->ev_pre,
+                          s->ev_passed})
         if (ev) hipEventDestroy(ev);
     if (s->graves_h) hipHostFree(s->graves_h);
     if (s->ring_mem) hipHostFree(s->ring_mem);
