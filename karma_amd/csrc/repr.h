@@ -11,7 +11,9 @@
 // float-to-string conversion", PLDI 2018), restated here on 128-bit products
 // of the mantissa with the power-of-5 tables of repr_tables.h.  Parity with
 // CPython is tested on the host build of this header (tests/test_repr_cpu.py)
-// and through the edge-list kernel on the GPU.
+// and, on the GPU, over the whole f64 range through both device paths: repr_f64
+// in the edge-list kernels and parts / parts_write in the one-launch view
+// summary (tests/test_gpu_consumers_device.py).
 #pragma once
 #include <hip/hip_runtime.h>
 
