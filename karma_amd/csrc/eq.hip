@@ -480,7 +480,7 @@ int graph_eq_run(karma_ctx* ctx, const int64_t* cls_off, const uint32_t* members
     hipEvent_t* ev = ctx->xfer_ev;
     if (!is_device) {
         KARMA_TRY(ctx_fork(ctx));
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 5; ++i)
             if (!ev[i]) KARMA_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
         xs = ctx->fork_stream;
         KARMA_TRY(d_off.alloc(ctx, C + 1));
@@ -507,7 +507,13 @@ int graph_eq_run(karma_ctx* ctx, const int64_t* cls_off, const uint32_t* members
         cnt = d_cnt.ptr;
         KARMA_HIP(hipStreamWaitEvent(ms, ev[1], 0));
         // the class offsets and skip flags from the sizes, in one scan
-        if (compact) KARMA_TRY(scan_excl_sizes(ctx, d_sz.ptr, d_skip.ptr, C, d_off.ptr));
+        if (compact) {
+            KARMA_TRY(scan_excl_sizes(ctx, d_sz.ptr, d_skip.ptr, C, d_off.ptr));
+            // the totals search these offsets from the fork stream: it waits for
+            // this scan before they start (nothing else orders the two streams
+            // when the scratch is sized speculatively and the host does not wait)
+            KARMA_HIP(hipEventRecord(ev[4], ms));
+        }
     } else {
         KARMA_HIP(hipMemsetAsync(zero.ptr, 0, (seg_words + 1 + 4) * 8, ms));
     }
@@ -579,6 +585,7 @@ int graph_eq_run(karma_ctx* ctx, const int64_t* cls_off, const uint32_t* members
     {
         StreamScope on_xs(ctx, xs);
         if (N) KARMA_HIP(hipMemsetAsync(p->totals.ptr, 0, N * 8, xs));
+        if (compact) KARMA_HIP(hipStreamWaitEvent(xs, ev[4], 0));  // the offsets scanned on the main stream
         if (n_mem || compact)  // (compact: also checks the sizes' sum against n_mem)
             KARMA_LAUNCH(ctx, "eq_totals", eq_totals_kernel, grid_of(n_mem, kEqT), kEqT, 0, in, n_mem,
                          (unsigned long long*)p->totals.ptr, bad);

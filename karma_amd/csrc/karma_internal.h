@@ -107,7 +107,7 @@ struct karma_ctx {
     // unless the job's caller brings a stream of its own (SetsOpts::fork)
     hipStream_t fork_stream = nullptr;
     hipEvent_t fork_a = nullptr, fork_b = nullptr;
-    hipEvent_t xfer_ev[4] = {};  // the eq path's staged host->device copies on fork_stream
+    hipEvent_t xfer_ev[5] = {};  // the eq path's staged host->device copies on fork_stream ([4]: the compact offsets)
     int64_t eq_pair_cap = 0;     // the eq path's previous pair total (its speculative scratch size)
 };
 
