@@ -225,7 +225,7 @@ int karma_kmer_row_totals(karma_kmer_plan* p, int64_t* dst_host);
  * counts (and, for eq classes, the first emission position). */
 typedef struct karma_pairs karma_pairs;
 #define KARMA_REC_SORTED 0   /* records grouped by read, read ids non-decreasing (SAM order) */
-#define KARMA_REC_UNSORTED 1 /* any order: sorted by read on the device first */
+#define KARMA_REC_UNSORTED 1 /* any order: sorted by read on the device first, then run as KARMA_REC_FLAGGED words */
 #define KARMA_REC_FLAGGED 2  /* records as n_records x u32: contig | (first record of its read) << 31, grouped by
                               * read.  The graph depends only on which records share a read (read_graph.py:31-49
                               * intersects readsets), so the read ids give way to read-start flags: 4 bytes per
@@ -233,7 +233,8 @@ typedef struct karma_pairs karma_pairs;
                               * The words no longer carry read ids, so the format itself cannot be checked for
                               * grouping (records of ids A, B, A are three reads here, where KARMA_REC_SORTED
                               * reports KARMA_ERR_UNSORTED): whoever makes the words checks it, as
-                              * karma_amd.engine.flag_records does (ValueError when read ids decrease). */
+                              * karma_records_flag does on the device (KARMA_ERR_UNSORTED when read ids
+                              * decrease) and karma_amd.engine.flag_records on the host (ValueError). */
 /* records: n_records x {u32 read_id, u32 contig} interleaved (or, flags =
  * KARMA_REC_FLAGGED, n_records x u32 flagged contigs; records is then a
  * uint32_t array of n_records entries).  Deduplicates
@@ -257,6 +258,30 @@ int karma_graph_records_end(karma_graph_job* job, karma_pairs** out);
  * bounds then answers without a launch or a synchronisation.  Applies to one
  * job; at most 64 ranks. */
 int karma_graph_split_hint(karma_ctx* ctx, const int64_t* bounds, int nranks);
+/* {u32 read, u32 contig} pairs -> KARMA_REC_FLAGGED words, on the device: the
+ * producer of the format for a caller whose pairs are on the host or already
+ * in HBM (the words then go to karma_graph_records / karma_step_run).
+ * rec_format: KARMA_REC_SORTED (read ids must not decrease: KARMA_ERR_UNSORTED
+ * otherwise, the pairs path's own condition and message) or KARMA_REC_UNSORTED
+ * (stably sorted by read id on the device first, so the words are a function
+ * of the input alone; < 2^31 records, as karma_graph_records).  A contig id
+ * >= 2^31 is KARMA_ERR_ARG.  records: n_records pairs, host (is_device = 0) or
+ * device, any 4-byte alignment; out: n_records u32, host or device, any 4-byte
+ * alignment (pointers off a 16-byte boundary go through an aligned temporary);
+ * ranges that overlap are KARMA_ERR_ARG.  n_reads (may be NULL): the number of
+ * flag bits set.  Synchronises the stream once; after an error the contents of
+ * out are unspecified.  n_records == 0: nothing written, *n_reads = 0.
+ * (A karma_graph_records job on KARMA_REC_UNSORTED records takes the same
+ * route by itself: sort, flagged words, the flagged classify.) */
+int karma_records_flag(karma_ctx* ctx, const uint32_t* records, int64_t n_records, int rec_format, int is_device,
+                       uint32_t* out, int out_is_device, int64_t* n_reads);
+/* The sorted kernel's tile, for tests that place cases on its edges: records
+ * per thread (one 16-byte store), per wave and per block. */
+int karma_records_flag_tile(int* per_thread, int* per_wave, int* per_block);
+/* For tests: launches of the records job's classify kernel this thread has
+ * made, by the record format it read (pairs; flagged words).  A function of
+ * the call sequence alone, like karma_api_calls. */
+int karma_classify_launches(uint64_t* pairs, uint64_t* flagged);
 /* For tests: the resident blocks per compute unit (the occupancy query, with
  * the job's dynamic LDS) of the classify kernel a records job of n_contigs in
  * rec_format (KARMA_REC_SORTED or KARMA_REC_FLAGGED) would launch. */

@@ -114,6 +114,9 @@ _SIGS = {
     "karma_graph_records_end": [_c_p, _PP],
     "karma_graph_split_hint": [_c_p, _c_p, _i32],
     "karma_graph_classify_occupancy": [_c_p, _i64, _i32, ctypes.POINTER(ctypes.c_int)],
+    "karma_records_flag": [_c_p, _c_p, _i64, _i32, _i32, _c_p, _i32, _I64P],
+    "karma_records_flag_tile": [ctypes.POINTER(ctypes.c_int)] * 3,
+    "karma_classify_launches": [_c_p, _c_p],
     "karma_graph_eq": [_c_p, _c_p, _c_p, _c_p, _c_p, _i64, _i64, _i32, _PP],
     "karma_graph_eq_compact": [_c_p, _c_p, _c_p, _i64, _c_p, _i64, _i64, _PP],
     "karma_pairs_merge": [_c_p, _c_p, _c_p, _i64, _i32, _PP],
@@ -451,6 +454,21 @@ def api_calls():
     n = ctypes.c_uint64(0)
     call("karma_api_calls", ctypes.byref(n))
     return n.value
+
+
+def classify_launches():
+    """(pairs, flagged): launches of the records job's classify kernel this
+    thread has made, by the record format it read (karma_classify_launches)."""
+    p, f = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    call("karma_classify_launches", ctypes.byref(p), ctypes.byref(f))
+    return p.value, f.value
+
+
+def flag_tile():
+    """(records per thread, per wave, per block) of karma_records_flag's sorted kernel."""
+    v = [ctypes.c_int(0) for _ in range(3)]
+    call("karma_records_flag_tile", *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v)
 
 
 def dtype_code(dtype):

@@ -12,6 +12,7 @@ namespace karma {
 
 static thread_local std::string g_err;
 thread_local uint64_t t_hip_calls = 0;
+thread_local uint64_t t_classify_launches[2] = {0, 0};
 
 void set_error(const char* fmt, ...) {
     char buf[1024];
@@ -230,6 +231,13 @@ const char* karma_last_error(void) { return g_err.c_str(); }
 int karma_api_calls(uint64_t* n) {
     KARMA_CHECK(n, KARMA_ERR_ARG, "null out");
     *n = t_hip_calls;
+    return KARMA_OK;
+}
+
+int karma_classify_launches(uint64_t* pairs, uint64_t* flagged) {
+    KARMA_CHECK(pairs && flagged, KARMA_ERR_ARG, "null out");
+    *pairs = t_classify_launches[0];
+    *flagged = t_classify_launches[1];
     return KARMA_OK;
 }
 

@@ -301,12 +301,6 @@ __global__ void __launch_bounds__(kOrdT) eq_order_kernel(const uint32_t* __restr
     }
 }
 
-__global__ void interleave_kernel(const uint32_t* __restrict__ rid, const uint32_t* __restrict__ cid, int64_t n,
-                                  uint2* __restrict__ out) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = make_uint2(rid[i], cid[i]);
-}
-
 __global__ void deinterleave_kernel(const uint2* __restrict__ in, int64_t n, uint32_t* __restrict__ rid,
                                     uint32_t* __restrict__ cid) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -588,6 +582,23 @@ int sort_reduce_pairs(karma_ctx* ctx, const uint64_t* keys_in, const int64_t* co
     return KARMA_OK;
 }
 
+int records_sorted_columns(karma_ctx* ctx, const uint2* rec, int64_t A, DevArray<uint32_t>& rid,
+                           DevArray<uint32_t>& cid) {
+    KARMA_CHECK(A >= 1 && A < (int64_t(1) << 31), KARMA_ERR_ARG, "unsorted path limited to 2^31 records");
+    KARMA_TRY(rid.alloc(ctx, A));
+    KARMA_TRY(cid.alloc(ctx, A));
+    if (A == 1) {  // nothing to sort
+        KARMA_LAUNCH(ctx, "deinterleave", deinterleave_kernel, 1, 256, 0, rec, A, rid.ptr, cid.ptr);
+        return KARMA_OK;
+    }
+    DevArray<uint32_t> rid0, cid0;
+    KARMA_TRY(rid0.alloc(ctx, A));
+    KARMA_TRY(cid0.alloc(ctx, A));
+    KARMA_LAUNCH(ctx, "deinterleave", deinterleave_kernel, grid1(A), 256, 0, rec, A, rid0.ptr, cid0.ptr);
+    // grouped by read: the library's radix sort on the read ids (sort.hip)
+    return radix_sort_u32(ctx, rid0.ptr, cid0.ptr, A, 32, rid.ptr, cid.ptr);
+}
+
 }  // namespace karma
 
 struct karma_graph_job {
@@ -615,10 +626,30 @@ int karma::graph_records_begin(karma_ctx* ctx, const uint32_t* records, int64_t 
     DevArray<uint32_t> ownw;
     const uint2* rec = reinterpret_cast<const uint2*>(records);
     int rc = KARMA_OK;
-    if (flags == KARMA_REC_FLAGGED) {
+    if (flags == KARMA_REC_FLAGGED || flags == KARMA_REC_UNSORTED) {
         // one u32 per record; the classify kernel streams 16-byte loads
         const uint32_t* w = records;
-        if (!is_device || (reinterpret_cast<uintptr_t>(w) & 15)) {
+        if (flags == KARMA_REC_UNSORTED) {
+            // grouped by read on the device (the library's radix sort on the
+            // read ids, sort.hip), then straight to flagged words from the
+            // sorted columns: the job runs the flagged classify.  A contig id
+            // >= 2^31 reaches it as 2^31 - 1, which it reports as any id >= n_contigs.
+            KARMA_CHECK(A < (int64_t(1) << 31), KARMA_ERR_ARG, "unsorted path limited to 2^31 records");
+            if (A && (!is_device || (reinterpret_cast<uintptr_t>(records) & 7))) {
+                if ((rc = own.alloc(ctx, A))) return rc;
+                KARMA_HIP(hipMemcpyAsync(own.ptr, records, A * 8,
+                                         is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+                rec = own.ptr;
+            }
+            if ((rc = ownw.alloc(ctx, std::max<int64_t>(A, 1)))) return rc;
+            if (A) {
+                DevArray<uint32_t> rid, cid;
+                if ((rc = records_sorted_columns(ctx, rec, A, rid, cid)) ||
+                    (rc = flag_sorted_columns(ctx, rid.ptr, cid.ptr, A, ownw.ptr, nullptr)))
+                    return rc;
+            }
+            w = ownw.ptr;
+        } else if (!is_device || (reinterpret_cast<uintptr_t>(w) & 15)) {
             if ((rc = ownw.alloc(ctx, std::max<int64_t>(A, 1)))) return rc;
             if (A)
                 KARMA_HIP(hipMemcpyAsync(ownw.ptr, records, A * 4,
@@ -640,23 +671,12 @@ int karma::graph_records_begin(karma_ctx* ctx, const uint32_t* records, int64_t 
         *out = job;
         return KARMA_OK;
     }
-    if (!is_device || flags == KARMA_REC_UNSORTED) {
+    if (!is_device) {
         if ((rc = own.alloc(ctx, A))) return rc;
         if (A) {
-            KARMA_HIP(hipMemcpyAsync(own.ptr, records, A * 8, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                     ctx->stream));
+            KARMA_HIP(hipMemcpyAsync(own.ptr, records, A * 8, hipMemcpyHostToDevice, ctx->stream));
         }
         rec = own.ptr;
-    }
-    if (flags == KARMA_REC_UNSORTED && A > 1) {
-        KARMA_CHECK(A < (int64_t(1) << 31), KARMA_ERR_ARG, "unsorted path limited to 2^31 records");
-        DevArray<uint32_t> rid, cid, rid2, cid2;
-        if ((rc = rid.alloc(ctx, A)) || (rc = cid.alloc(ctx, A)) || (rc = rid2.alloc(ctx, A)) ||
-            (rc = cid2.alloc(ctx, A))) return rc;
-        KARMA_LAUNCH(ctx, "deinterleave", deinterleave_kernel, grid1(A), 256, 0, own.ptr, A, rid.ptr, cid.ptr);
-        // grouped by read: the library's radix sort on the read ids (sort.hip)
-        if ((rc = radix_sort_u32(ctx, rid.ptr, cid.ptr, A, 32, rid2.ptr, cid2.ptr))) return rc;
-        KARMA_LAUNCH(ctx, "interleave", interleave_kernel, grid1(A), 256, 0, rid2.ptr, cid2.ptr, A, own.ptr);
     }
     if (reinterpret_cast<uintptr_t>(rec) & 15) {  // the set pipeline streams 16-byte loads
         if (!own.ptr) {

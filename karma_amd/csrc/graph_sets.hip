@@ -2534,6 +2534,7 @@ int records_to_pairs_wide(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, karma
                         n_gen.ptr, blk_items.ptr, 1,     big_list.ptr, counters,  flags,
                         nullptr,   0,         0,       nullptr, 0, nullptr, kCChunk};
             C.recw = rec.fw;
+            ++t_classify_launches[rec.flagged() ? 1 : 0];
             if (rec.flagged())
                 KARMA_LAUNCH(ctx, "graph_classify", (classify2_kernel<false, false, false, false, true>),
                              ceil_div(n_chunks, kCW / 64), kCW, 0, C, BinArgs{});
@@ -3016,6 +3017,7 @@ int SetsJob::launch() {
             C.c0 = c_from;
             const int64_t cg = ceil_div(c_to - c_from, kCW / 64);
             if (cg <= 0) return KARMA_OK;
+            ++t_classify_launches[rec.flagged() ? 1 : 0];
             return with_classify(rec.flagged(), append, bin, relabeled, [&](auto kern) -> int {
                 KARMA_LAUNCH(ctx, "graph_classify", kern, cg, kCW, bin ? class_bin_lds(g.Bc) : 0, C, Bn);
                 return KARMA_OK;

@@ -343,4 +343,16 @@ int graph_records_begin(karma_ctx* ctx, const uint32_t* records, int64_t A, int6
                         const SetsOpts& opts, karma_graph_job** out);
 // Frees a deferred job's buffers to the allocator (stream-ordered; no wait).
 void sets_release(SetsJob* job);
+// graph.hip: device pairs (8-byte aligned) as two columns stably sorted by read
+// id (deinterleave + the library's radix sort; A < 2^31), allocated here
+int records_sorted_columns(karma_ctx* ctx, const uint2* rec, int64_t A, DevArray<uint32_t>& rid,
+                           DevArray<uint32_t>& cid);
+// flag.hip: KARMA_REC_FLAGGED words of such columns (16-byte aligned, as the
+// allocator's blocks are), a contig id >= 2^31 written as 2^31 - 1.  ctrl: null,
+// or 3 zeroed words {unused, an id >= 2^31 seen, read count}.
+int flag_sorted_columns(karma_ctx* ctx, const uint32_t* rid, const uint32_t* cid, int64_t n, uint32_t* out,
+                        unsigned long long* ctrl);
+// Launches of the records job's classify kernel on this thread, by record
+// format: [0] pairs, [1] flagged words (karma_classify_launches)
+extern thread_local uint64_t t_classify_launches[2];
 }  // namespace karma

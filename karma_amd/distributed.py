@@ -396,13 +396,20 @@ class ShardedBuild:
         for c in self.contexts():
             c.sync()
 
-    def run(self, store, records, n_records, keep=False, sequential=False, count=True):
-        """One step.  sequential=True keeps the profile on the main stream (no
+    def run(self, store, records, n_records=None, keep=False, sequential=False, count=True):
+        """One step.  records: a device address (with n_records), or, in a
+        flagged build, an engine.FlaggedRecords (engine.flag_records_device),
+        which the caller keeps alive until the step's outputs are read.
+        sequential=True keeps the profile on the main stream (no
         side stream): slower, but every kernel has the chip to itself, which is
         what a per-kernel timing pass wants.  count=False (a step of a stream
         of identical steps; with an exchange only): the owner's edge count is
         not read back, so the step ends without waiting for its last kernels,
         and stats["E_local"] is None."""
+        if hasattr(records, "n_reads") and hasattr(records, "ptr"):  # engine.FlaggedRecords
+            if not self.flagged:
+                raise ValueError("FlaggedRecords need a ShardedBuild(flagged=True)")
+            records, n_records = records.ptr, records.n_records
         if self.native is not None:
             return self.native.run(store, records, n_records, keep=keep, sequential=sequential, count=count,
                                    flagged=self.flagged)

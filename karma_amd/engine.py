@@ -330,6 +330,76 @@ class GraphJob:
                 pass
 
 
+class FlaggedRecords:
+    """KARMA_REC_FLAGGED words in device memory, made by flag_records_device
+    (karma_records_flag).  Owns its buffer: keep it alive while a job reads it.
+    .ptr: the device address, .n_records: the word count, .n_reads: the number
+    of flag bits set, .to_host(): the words as a uint32 array."""
+
+    def __init__(self, ctx, buf, n_records, n_reads):
+        self.ctx, self._buf, self.n_records, self.n_reads = ctx, buf, int(n_records), int(n_reads)
+
+    @property
+    def ptr(self):
+        return self._buf.ptr
+
+    def to_host(self):
+        return self._buf.numpy()[: self.n_records]
+
+    def close(self):
+        if self._buf is not None:
+            self._buf.close()
+            self._buf = None
+
+
+def _pairs_array(records):
+    """Host records as a C-order uint32[n, 2] array (ValueError / TypeError otherwise)."""
+    a = np.asarray(records)
+    if a.size == 0:
+        return np.zeros((0, 2), np.uint32)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"records must be integers (uint32 read and contig ids), not {a.dtype}")
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"records must have shape (n, 2): (read id, contig id) rows, not {a.shape}")
+    if a.dtype != np.uint32 and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+        raise ValueError("read and contig ids must fit 32 unsigned bits")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def flag_records_device(records=None, *, device_ptr=None, n_records=None, grouped=True, ctx=None):
+    """(read, contig) records -> KARMA_REC_FLAGGED words in device memory
+    (karma_records_flag): the device twin of flag_records, for records on the
+    host (records: uint32[n, 2]) or already in HBM (device_ptr, n_records).
+    grouped=True: read ids must not decrease (KarmaError, KARMA_ERR_UNSORTED);
+    grouped=False: any order, stably sorted by read id on the device first.
+    A contig id >= 2^31 is a KarmaError (KARMA_ERR_ARG).  Returns FlaggedRecords."""
+    if (records is None) == (device_ptr is None):
+        raise ValueError("give either records (a host array) or device_ptr (with n_records)")
+    fmt = _lib.KARMA_REC_SORTED if grouped else _lib.KARMA_REC_UNSORTED
+    if device_ptr is not None:
+        if n_records is None:
+            raise ValueError("device_ptr needs n_records")
+        n = int(n_records)
+        if n < 0:
+            raise ValueError("n_records must not be negative")
+        src, on_device = ctypes.c_void_p(int(device_ptr)), 1
+    else:
+        if n_records is not None:
+            raise ValueError("n_records goes with device_ptr; host records carry their own length")
+        rec = _pairs_array(records)
+        n = len(rec)
+        src, on_device = (ptr(rec) if n else None), 0
+    ctx = ctx or _lib.default_context()
+    buf = _lib.DevBuf(ctx, (max(n, 1),), np.uint32)
+    reads = ctypes.c_int64(0)
+    try:
+        call("karma_records_flag", ctx.h, src, n, fmt, on_device, ctypes.c_void_p(buf.ptr), 1, ctypes.byref(reads))
+    except Exception:
+        buf.close()
+        raise
+    return FlaggedRecords(ctx, buf, n, reads.value)
+
+
 class Pairs:
     """Sorted unique (a << 32 | b, count) list (karma_pairs)."""
 
@@ -338,8 +408,12 @@ class Pairs:
 
     @classmethod
     def from_records(cls, ctx, records, n_contigs, grouped=True, device_ptr=None, n_records=None, flagged=False):
-        """flagged: the records are KARMA_REC_FLAGGED words (flag_records), one u32 each."""
+        """flagged: the records are KARMA_REC_FLAGGED words (flag_records), one u32 each.
+        A FlaggedRecords (flag_records_device) may stand for records or device_ptr."""
         h = ctypes.c_void_p()
+        fr = device_ptr if isinstance(device_ptr, FlaggedRecords) else records
+        if isinstance(fr, FlaggedRecords):
+            device_ptr, n_records, flagged = fr.ptr, fr.n_records, True
         flags = _lib.KARMA_REC_FLAGGED if flagged else _lib.KARMA_REC_SORTED if grouped else _lib.KARMA_REC_UNSORTED
         if device_ptr is not None:
             call("karma_graph_records", ctx.h, ctypes.c_void_p(device_ptr), n_records, n_contigs, flags, 1,
@@ -352,11 +426,16 @@ class Pairs:
         return cls(ctx, h)
 
     @classmethod
-    def from_records_begin(cls, ctx, n_contigs, device_ptr, n_records, grouped=True, split_bounds=None,
+    def from_records_begin(cls, ctx, n_contigs, device_ptr, n_records=None, grouped=True, split_bounds=None,
                            flagged=False):
         """First half of from_records on device records (karma_graph_records_begin):
         the pipeline is enqueued up to its host synchronisation; .end() finishes.
+        device_ptr: a device address (with n_records), or a FlaggedRecords.
         split_bounds: owner bounds the list will be split at (karma_graph_split_hint)."""
+        keep = None
+        if isinstance(device_ptr, FlaggedRecords):  # n_records may be None: the words' own count
+            keep = device_ptr
+            device_ptr, n_records, flagged = keep.ptr, keep.n_records, True
         if split_bounds is not None:
             b = np.ascontiguousarray(split_bounds, np.int64)
             call("karma_graph_split_hint", ctx.h, ptr(b), len(b) - 1)
@@ -364,7 +443,9 @@ class Pairs:
         flags = _lib.KARMA_REC_FLAGGED if flagged else _lib.KARMA_REC_SORTED if grouped else _lib.KARMA_REC_UNSORTED
         call("karma_graph_records_begin", ctx.h, ctypes.c_void_p(device_ptr), n_records, n_contigs, flags, 1,
              ctypes.byref(h))
-        return GraphJob(cls, ctx, h)
+        job = GraphJob(cls, ctx, h)
+        job.records = keep  # the words stay alive until the job ends
+        return job
 
     @classmethod
     def from_eq(cls, ctx, cls_off, members, counts, pair_skip, n_contigs):

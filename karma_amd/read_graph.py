@@ -170,6 +170,7 @@ class ReadGraph(nx.Graph):
         self._mirror_dirty = False  # nodes removed since the mirror was taken
         self._view_root = None      # mirror this graph is a (node-removed) view copy of
         self._summary = None        # one-launch consumer results of a small view copy
+        self._records = None        # engine.FlaggedRecords of from_sam(keep_records=True)
         src = incoming_graph_data
         # nx.Graph(G.subgraph(nodes)) / nx.Graph(G) of a mirrored ReadGraph: the
         # copy's layout is derived from G's on the device
@@ -246,16 +247,24 @@ class ReadGraph(nx.Graph):
         return cls(incoming_graph_data=graph)
 
     @classmethod
-    def from_sam(cls, sam, skip_headers: bool = True, threads: int = 0) -> "ReadGraph":
+    def from_sam(cls, sam, skip_headers: bool = True, threads: int = 0, keep_records: bool = False) -> "ReadGraph":
         """from_contigs over the contigs of SAM lines (contig.py:24,34 readsets,
         grouped by RNAME in order of first appearance) without building Python
-        readsets: the C++ reader's (read, contig) records go straight to the GPU."""
+        readsets: the C++ reader's (read, contig) records go straight to the GPU.
+        keep_records: the records' KARMA_REC_FLAGGED words (engine.FlaggedRecords,
+        read-sorted on the device) stay on the returned graph as ._records, for a
+        caller that goes on to ShardedBuild or karma_step_run without parsing twice."""
         rec, _ = load_sam_records(sam, skip_headers, threads)
         names = rec.rnames
+        records = engine.flag_records_device(rec.records, grouped=False) if keep_records else rec.records
         if len(names) < 2:
-            return cls(incoming_graph_data=nx.Graph())
-        e = _edges_or_zero_div(engine.graph_from_records, rec.records, len(names), grouped=False)
-        return cls._from_edge_list(list(names), e.a, e.b, e.weight)
+            out = cls(incoming_graph_data=nx.Graph())
+        else:
+            e = _edges_or_zero_div(engine.graph_from_records, records, len(names), grouped=False)
+            out = cls._from_edge_list(list(names), e.a, e.b, e.weight)
+        if keep_records:
+            out._records = records
+        return out
 
     def set_original_contigs(self, original_contigs: list) -> None:
         self.original_contigs = original_contigs
