@@ -220,6 +220,42 @@ int karma_ctx_set_side_headroom(karma_ctx* ctx, int blocks_per_cu);
 /* Number of k-mer occurrences per contig (0 => the all-zero row of kmer.py:250-258). */
 int karma_kmer_row_totals(karma_kmer_plan* p, int64_t* dst_host);
 
+/* ---- exact k nearest neighbours of matrix rows (the profile's kNN graph) ---- */
+/* x: row-major f64, n rows, m columns, row stride ld >= m (in doubles), on the
+ * host (x_is_device = 0: copied up) or the device.  For every query row i in
+ * [row_lo, row_hi) writes its k nearest rows among all n, itself included:
+ *
+ *   distance  d2(i, j) is accumulated over the columns c = 0 ... m - 1 in that
+ *             order from +0.0: t = x[i,c] - x[j,c]; acc = acc + t * t, each of
+ *             the three a single IEEE round-to-nearest f64 operation, no
+ *             contraction, subnormals kept: what numpy computes elementwise.
+ *             d2(i, j) and d2(j, i) are bit-identical.
+ *   order     the k rows j in [0, n) with the smallest (d2(i, j), j),
+ *             lexicographically, ascending.  d2 >= +0, so the u64 bit patterns
+ *             order the same way.  Row i is not special: it usually comes
+ *             first, but a duplicate row with a lower index precedes it.
+ *   outputs   idx: int32 (row_hi - row_lo) x k row-major; dist: f64 of the same
+ *             shape, the correctly rounded sqrt(d2).  The order is by d2, not
+ *             by the rounded root.  Host or device (out_is_device).
+ *   limits    1 <= k <= min(n, k_max) (karma_knn_tile; 64); n < 2^31.  n == 0
+ *             or row_lo == row_hi: nothing is written, KARMA_OK (pointers and k
+ *             are then not looked at).
+ *
+ * Non-finite inputs (NaN, +-inf) are outside the contract: the k-mer profile
+ * never holds them.  d2 = +inf that overflows from finite inputs is inside it
+ * and ties by index like any other value.  Padding beyond column m of a row is
+ * never read.
+ * KARMA_ERR_ARG with a message: a null pointer, k out of range, ld < m, a row
+ * range not within 0 <= row_lo <= row_hi <= n, x or dist off an 8-byte boundary
+ * (idx: 4-byte), a byte size that overflows.  KARMA_ERR_OOM: no memory for the
+ * copy of a host x or for host outputs' device twins.  Synchronises the stream
+ * once before returning.  Kernel name in the timing table: profile_knn. */
+int karma_knn_rows(karma_ctx* ctx, const double* x, int64_t n, int64_t m, int64_t ld, int x_is_device,
+                   int64_t row_lo, int64_t row_hi, int k, int32_t* idx, double* dist, int out_is_device);
+/* The kernel's tile, for tests that place cases on its edges: query rows per
+ * block, candidate rows per step, columns staged at a time, the largest k. */
+int karma_knn_tile(int* query_rows, int* cand_rows, int* col_panel, int* k_max);
+
 /* ---- shared-read graph ----------------------------------------------------- */
 /* A pair list: unique keys (a << 32 | b, a <= b) sorted ascending with int64
  * counts (and, for eq classes, the first emission position). */

@@ -109,6 +109,8 @@ _SIGS = {
     "karma_ctx_join": [_c_p, _c_p],
     "karma_ctx_set_side_headroom": [_c_p, _i32],
     "karma_kmer_row_totals": [_c_p, _c_p],
+    "karma_knn_rows": [_c_p, _c_p, _i64, _i64, _i64, _i32, _i64, _i64, _i32, _c_p, _c_p, _i32],
+    "karma_knn_tile": [ctypes.POINTER(ctypes.c_int)] * 4,
     "karma_graph_records": [_c_p, _c_p, _i64, _i64, _i32, _i32, _PP],
     "karma_graph_records_begin": [_c_p, _c_p, _i64, _i64, _i32, _i32, _PP],
     "karma_graph_records_end": [_c_p, _PP],
@@ -468,6 +470,13 @@ def flag_tile():
     """(records per thread, per wave, per block) of karma_records_flag's sorted kernel."""
     v = [ctypes.c_int(0) for _ in range(3)]
     call("karma_records_flag_tile", *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def knn_tile():
+    """(query rows per block, candidate rows per step, columns staged at a time, largest k) of karma_knn_rows."""
+    v = [ctypes.c_int(0) for _ in range(4)]
+    call("karma_knn_tile", *[ctypes.byref(x) for x in v])
     return tuple(x.value for x in v)
 
 

@@ -113,6 +113,17 @@ class DeviceProfile:
             raise ValueError("DeviceProfile is closed")
         return self._buf.numpy().reshape(self.shape)
 
+    def knn(self, k, row_lo=0, row_hi=None):
+        """The profile's exact k-nearest-neighbour lists, computed where it
+        lies (engine.knn_rows; the contract is in include/karma.h): (idx
+        int32[rows, k], dist float64[rows, k]) as numpy arrays for the rows
+        [row_lo, row_hi), every row among its own neighbours."""
+        if self._closed or self._buf is None:
+            raise ValueError("DeviceProfile is closed")
+        from . import engine
+
+        return engine.knn_rows(self, k, row_lo, row_hi, ctx=self.ctx)
+
     @property
     def __cuda_array_interface__(self):
         return {"shape": self.shape, "typestr": "<f8", "data": (self.ptr, False), "strides": None,

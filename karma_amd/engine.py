@@ -306,6 +306,67 @@ def kmer_profile_device(sequences, kmer_size, ctx=None):
     return dev, cols, tot
 
 
+def _knn_source(x):
+    """(host array or None, device pointer or None, n, M, ld) of a matrix knn_rows accepts."""
+    from .device_profile import DeviceProfile
+
+    if isinstance(x, DeviceProfile):
+        if x._buf is None:
+            raise ValueError("DeviceProfile is closed")
+        n, M = x.shape
+        return None, x.ptr, n, M, M
+    if isinstance(x, _lib.DevBuf):
+        if len(x.shape) != 2 or x.dtype != np.float64:
+            raise ValueError(f"a device matrix must be float64 (n, M), not {x.dtype} {x.shape}")
+        if x.ptr is None:
+            raise ValueError("DevBuf is closed")
+        n, M = x.shape
+        return None, x.ptr, n, M, M
+    a = np.asarray(x)
+    if a.dtype != np.float64:
+        raise TypeError(f"the matrix must be float64 (distances are defined on its bits), not {a.dtype}")
+    if a.ndim != 2:
+        raise ValueError(f"the matrix must have shape (n, M), not {a.shape}")
+    n, M = a.shape
+    # rows of a wider C-order array keep their stride (ld); anything else is copied compact
+    if not (n and M and a.strides[1] == 8 and a.strides[0] >= 8 * M and a.strides[0] % 8 == 0):
+        a = np.ascontiguousarray(a)
+    return a, None, n, M, (a.strides[0] // 8 if n and M else M)
+
+
+def knn_rows(x, k, row_lo=0, row_hi=None, ctx=None, out_device=False):
+    """Exact k nearest rows of the float64 matrix x (n, M) for the query rows
+    [row_lo, row_hi) (karma_knn_rows; the contract is in include/karma.h):
+    d2 accumulated column by column as acc + t * t, the k smallest (d2, index)
+    among all n rows, the row itself included.  x: a numpy array, a DevBuf or a
+    DeviceProfile.  Returns (idx int32[rows, k], dist float64[rows, k]): numpy
+    arrays, or DevBufs with out_device=True.  1 <= k <= min(n, 64); an empty
+    range gives empty arrays."""
+    host, dptr, n, M, ld = _knn_source(x)
+    k = int(k)
+    row_lo = int(row_lo)
+    row_hi = n if row_hi is None else int(row_hi)
+    if not 0 <= row_lo <= row_hi <= n:
+        raise ValueError(f"need 0 <= row_lo <= row_hi <= n, not [{row_lo}, {row_hi}) of {n} rows")
+    k_max = _lib.knn_tile()[3]
+    if k < 1 or (row_hi > row_lo and k > min(n, k_max)):
+        raise ValueError(f"need 1 <= k <= min(n, {k_max}), not k = {k} with n = {n}")
+    rows = row_hi - row_lo
+    if ctx is None:
+        ctx = x.ctx if host is None else _lib.default_context()
+    if out_device:
+        idx, dist = _lib.DevBuf(ctx, (rows, k), np.int32), _lib.DevBuf(ctx, (rows, k), np.float64)
+        pi, pd = ctypes.c_void_p(idx.ptr), ctypes.c_void_p(dist.ptr)
+    else:
+        idx, dist = np.empty((rows, k), np.int32), np.empty((rows, k), np.float64)
+        pi, pd = ptr(idx), ptr(dist)
+    if rows:
+        src = ctypes.c_void_p(dptr) if host is None else ptr(host)
+        call("karma_knn_rows", ctx.h, src, n, M, ld, 1 if host is None else 0, row_lo, row_hi, k, pi, pd,
+             1 if out_device else 0)
+    return idx, dist
+
+
 # ---------------------------------------------------------------------------
 # Graph
 # ---------------------------------------------------------------------------

@@ -8,6 +8,7 @@ reference (tests/test_gpu_parity.py).  The clustering tail (UMAP + HDBSCAN,
 kmer.py:283-301) is third-party and used only if those packages import.
 """
 
+import inspect
 import os
 import sys
 
@@ -68,6 +69,20 @@ class KmerClustering:
         same side effects and failure modes as __calc_kmer_profile."""
         return self.__profile(engine.kmer_profile_device)
 
+    def kmer_knn(self, neighbors):
+        """The profile and its exact neighbour graph, the search UMAP would
+        start with (kmer.py:283-290), computed on the device where the profile
+        lies: (profile float64[N, M] on the host, idx int32[N, neighbors],
+        dist float64[N, neighbors]), every row among its own neighbours
+        (include/karma.h, karma_knn_rows).  Same side effects and failure
+        modes as calc_kmer_profile_device."""
+        dev = self.calc_kmer_profile_device()
+        try:
+            idx, dist = dev.knn(neighbors)
+            return dev.numpy(), idx, dist
+        finally:
+            dev.close()
+
     def __profile(self, compute):
         logger.info("Extracting kmers from contigs.")
         try:
@@ -116,15 +131,26 @@ class KmerClustering:
             fh.write("\t".join(kwargs.keys()) + "\n")
             fh.write("\t".join(str(v) for v in kwargs.values()) + "\n")
 
-    def run(self, neighbors, components, dist, r_state, min_cluster_size):
+    def run(self, neighbors, components, dist, r_state, min_cluster_size, device_knn=False):
         """kmer.py:274-325.  The profile is computed on the GPU; UMAP/HDBSCAN
-        are the reference's third-party dependencies and must be importable."""
+        are the reference's third-party dependencies and must be importable.
+
+        device_knn (an addition; default off: nothing changes): the neighbour
+        search UMAP starts with runs on the device too (kmer_knn) and is handed
+        to umap.UMAP as precomputed_knn=(idx, dist), where the installed
+        umap-learn has that parameter; where it has not (the reference pins
+        0.3.9), a warning is logged and UMAP searches by itself."""
         if os.path.isfile(self.output_file):
             logger.info(f"Read from previous calculation: {self.output_file}")
             self.__read_clusters()
         else:
             logger.info("Calculate kmer profiles.")
-            kmer_profile = self.__calc_kmer_profile()
+            knn = None
+            if device_knn:
+                kmer_profile, knn_idx, knn_dist = self.kmer_knn(neighbors)
+                knn = (knn_idx, knn_dist)
+            else:
+                kmer_profile = self.__calc_kmer_profile()
             try:
                 import hdbscan
                 import umap
@@ -132,8 +158,13 @@ class KmerClustering:
                 raise ImportError("KmerClustering.run needs umap-learn and hdbscan (the reference's clustering "
                                   "dependencies); the k-mer profile itself does not") from e
             logger.info("Dimension reduction with UMAP.")
-            reduced = umap.UMAP(n_neighbors=neighbors, n_components=components, min_dist=dist,
-                                random_state=r_state).fit_transform(kmer_profile)
+            umap_args = dict(n_neighbors=neighbors, n_components=components, min_dist=dist, random_state=r_state)
+            if knn is not None:
+                if "precomputed_knn" in inspect.signature(umap.UMAP).parameters:
+                    umap_args["precomputed_knn"] = knn
+                else:
+                    logger.warning("This umap-learn takes no precomputed_knn: UMAP searches the neighbours itself.")
+            reduced = umap.UMAP(**umap_args).fit_transform(kmer_profile)
             logger.info(f"Perform clustering with HDBSCAN. (min_cluster_size: {min_cluster_size})")
             if min_cluster_size == 1:
                 clusterer = hdbscan.HDBSCAN(allow_single_cluster=True).fit(reduced)
