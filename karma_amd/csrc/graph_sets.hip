@@ -2559,7 +2559,10 @@ int records_to_pairs_wide(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, karma
         P = h[kCw];
         if (!hf[kFlagPairCap]) break;
         KARMA_CHECK(attempt == 0, KARMA_ERR_STATE, "pair list capacity exceeded twice");
-        pcap = kCChunk * 9 / 2;  // every read with <= 8 records fits
+        // every read with <= 8 records fits: u (u + 1) / 2 <= 4.5 u pairs from u
+        // records, and the reads that start in a chunk cover up to chunk + 7 records
+        // (the last may start at the chunk's last record)
+        pcap = (kCChunk + kMaxFast - 1) * 9 / 2;
     }
     DevArray<uint64_t> keys;
     DevArray<int64_t> ones;
@@ -2969,7 +2972,7 @@ int SetsJob::setup() {
 // One attempt: every kernel up to the control block readback (no host wait).
 int SetsJob::launch() {
     // pair lists: general reads' pairs per chunk; room for 1/8 pair per record
-    // first, the bound (4.5 per record) on a rerun
+    // first, the bound (4.5 per record its reads cover) on a rerun
     const int64_t max_pflush = n_pblk + ceil_div(n_chunks * pcap, PairStream::kCap) + 1;
     const int64_t pscap = n_chunks * pcap + max_pflush * (4 * (int64_t)B + 4);
     KARMA_TRY(plist.alloc(ctx, n_chunks * pcap));
@@ -3175,7 +3178,10 @@ int SetsJob::finish(karma_pairs* out) {
         if (!hf[kFlagPairCap]) break;
         KARMA_CHECK(attempt == 0, KARMA_ERR_STATE, "pair list capacity exceeded twice");
         attempt = 1;
-        pcap = chunk * 9 / 2;  // every read with <= 8 records fits
+        // every read with <= 8 records fits: u (u + 1) / 2 <= 4.5 u pairs from u
+        // records, and the reads that start in a chunk cover up to chunk + 7 records
+        // (general_kernel reads past the chunk's end for a read that starts in it)
+        pcap = (chunk + kMaxFast - 1) * 9 / 2;
         KARMA_TRY(launch());
     }
     const unsigned n_big = hc[kCtrBigReads];
