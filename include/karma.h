@@ -344,6 +344,10 @@ int karma_pairs_merge(karma_ctx* ctx, const uint64_t* keys, const int64_t* count
  * n_runs + 1 offsets starting at 0. */
 int karma_pairs_merge_runs(karma_ctx* ctx, const uint64_t* keys, const int64_t* counts, const int64_t* run_off,
                            int n_runs, int is_device, karma_pairs** out);
+/* The merge kernels' constants, for tests that place cases on their edges:
+ * elements of a run per block, window keys a block can stage in LDS, runs
+ * merged in one ranking pass, and lanes per window-bound search. */
+int karma_merge_tile(int* tile, int* lds_keys, int* max_runs, int* search_group);
 /* The exchange's wire format: n x {i64 key, i64 count} interleaved in device
  * memory.  _get_kc writes the list in it (stream-ordered, not waited for);
  * _merge_runs_kc merges received runs of it (at most 64 runs: without a host
@@ -376,7 +380,9 @@ typedef struct karma_edges karma_edges;
 #define KARMA_MODE_EQ 1    /* totals from the eq pass; diagonal pairs are self-loops */
 /* Edges with non-zero shared count and weight (s/tot[a] + s/tot[b]) / 2.
  * totals_dev: int64[n_contigs] device array, or NULL to take it from the pair
- * list (diagonal in READS mode, eq totals in EQ mode). */
+ * list (diagonal in READS mode, eq totals in EQ mode).  Contract (here and in
+ * karma_edges_begin; not checked): every contig id of the list is < n_contigs,
+ * and in READS mode with the totals taken from the list every key has a <= b. */
 int karma_edges_from_pairs(karma_ctx* ctx, karma_pairs* p, int mode, const int64_t* totals_dev, int64_t n_contigs,
                            karma_edges** out, int64_t* n_edges);
 /* The same in two halves, for an all-gather of the totals in between (the

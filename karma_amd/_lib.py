@@ -124,6 +124,7 @@ _SIGS = {
     "karma_pairs_merge": [_c_p, _c_p, _c_p, _i64, _i32, _PP],
     "karma_pairs_merge_runs": [_c_p, _c_p, _c_p, _c_p, _i32, _i32, _PP],
     "karma_pairs_merge_runs_kc": [_c_p, _c_p, _c_p, _i32, _PP],
+    "karma_merge_tile": [ctypes.POINTER(ctypes.c_int)] * 4,
     "karma_pairs_get_kc": [_c_p, _c_p],
     "karma_pairs_destroy": [_c_p],
     "karma_pairs_rebind": [_c_p, _c_p],
@@ -477,6 +478,14 @@ def knn_tile():
     """(query rows per block, candidate rows per step, columns staged at a time, largest k) of karma_knn_rows."""
     v = [ctypes.c_int(0) for _ in range(4)]
     call("karma_knn_tile", *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def merge_tile():
+    """(elements per block, staged window keys per block, runs per ranking pass, lanes per bound search) of
+    karma_pairs_merge_runs."""
+    v = [ctypes.c_int(0) for _ in range(4)]
+    call("karma_merge_tile", *[ctypes.byref(x) for x in v])
     return tuple(x.value for x in v)
 
 

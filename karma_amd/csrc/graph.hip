@@ -846,6 +846,13 @@ static int merge_runs_impl(karma_ctx* ctx, const uint64_t* keys, const int64_t* 
             KARMA_TRY(p->bad.alloc(ctx, 1));
             badp = p->bad.ptr;
             if (!tiles) KARMA_HIP(hipMemsetAsync(badp, 0, 8, ctx->stream));
+            // The ranking is a bijection only for sorted runs: after a descent
+            // two elements may land on one slot and another slot stays
+            // unwritten.  The list is handed on before the order flag is read,
+            // and its consumers index the totals by a and b (diag_totals_kernel,
+            // edges_write_kernel): an unwritten slot must hold a valid key,
+            // (0, 0), not whatever the allocation cache left there.
+            if (n) KARMA_HIP(hipMemsetAsync(kb[0].ptr, 0, n * 8, ctx->stream));
         }
         if (tiles) {
             DevArray<int64_t> wb;
@@ -940,6 +947,15 @@ static int merge_runs_impl(karma_ctx* ctx, const uint64_t* keys, const int64_t* 
     KARMA_CHECK(!h[1], KARMA_ERR_UNSORTED, "karma_pairs_merge_runs: a run is not sorted by key");
     p->n = h[0];
     *out = guard.release();
+    return KARMA_OK;
+}
+
+int karma_merge_tile(int* tile, int* lds_keys, int* max_runs, int* search_group) {
+    KARMA_CHECK(tile && lds_keys && max_runs && search_group, KARMA_ERR_ARG, "karma_merge_tile: null out");
+    *tile = kMergeTile;
+    *lds_keys = kMergeLds;
+    *max_runs = kMergeMaxRuns;
+    *search_group = kMG;
     return KARMA_OK;
 }
 
