@@ -256,6 +256,72 @@ int karma_knn_rows(karma_ctx* ctx, const double* x, int64_t n, int64_t m, int64_
  * block, candidate rows per step, columns staged at a time, the largest k. */
 int karma_knn_tile(int* query_rows, int* cand_rows, int* col_panel, int* k_max);
 
+/* ---- the same neighbour lists, one block of candidate rows at a time -------- */
+/* For profiles that are not one resident matrix (a sharded build's ranks, a
+ * streamed profile): per-query lists that outlive a call, folded with one
+ * block of candidate rows after another.  Distance, order and tie rule are
+ * karma_knn_rows' above; the result of folding every row once, in any block
+ * order, then karma_knn_finish, is bit for bit karma_knn_rows' of the whole
+ * matrix.
+ *
+ *   state     keys: u64 nq x k row-major, the d2 bit patterns; idx: int32 of
+ *             the same shape.  A row's entries are sorted ascending by
+ *             (key, index); an empty slot is (all-ones, INT32_MAX) and sorts
+ *             last.  Host or device (state_is_device; both arrays alike).
+ *   block     q: nq query rows, c: nc candidate rows, both row-major f64 of m
+ *             columns with row strides ldq, ldc >= m, each on the host (copied
+ *             up) or the device.  Candidate row r has index cand_base + r.  A
+ *             query row that is also among the candidates competes like any
+ *             other row.
+ *   result    each row's list becomes the k smallest (d2 bits, index) of
+ *             {its carried entries} and {this block's candidates}: an equal d2
+ *             with a lower index displaces a carried entry, so the order in
+ *             which blocks arrive does not matter.  first != 0: the incoming
+ *             state is not read (the lists start empty).  nc == 0: the state
+ *             stays as it is, or with first becomes all-empty lists.  nq == 0:
+ *             nothing is done.  m == 0: every d2 is +0.
+ *   split     cand_split = S >= 1: S slices of the block's candidate tiles
+ *             (contiguous, whole tiles of karma_knn_tile's cand_rows) run side
+ *             by side into partial lists in scratch memory, which a second
+ *             kernel merges with the carried list; S is clamped to the number
+ *             of tiles and to 32.  The lists do not depend on S.  0: the
+ *             library chooses (karma_knn_block_split tells what).
+ *   limits    1 <= k <= 64; k may exceed nc.  0 <= cand_base and
+ *             cand_base + nc <= 2^31 - 1.  nq < 2^31.  Inputs finite, as above.
+ *
+ * The caller's contract: across the calls (and merges) that feed one state no
+ * candidate index is offered twice; otherwise the lists are unspecified (no
+ * error, no fault).
+ * KARMA_ERR_ARG with a message, before anything is touched: negative shapes,
+ * ldq or ldc < m, cand_base out of range, k out of range, a negative
+ * cand_split, a null pointer, a matrix or keys off an 8-byte boundary (idx:
+ * 4-byte), a byte size that overflows.  Synchronises the stream once before
+ * returning.  Kernel names in the timing table: profile_knn_block, and with
+ * S > 1 one profile_knn_merge. */
+int karma_knn_block(karma_ctx* ctx, const double* q, int64_t nq, int64_t ldq, int q_is_device,
+                    const double* c, int64_t nc, int64_t ldc, int c_is_device,
+                    int64_t m, int64_t cand_base, int k,
+                    uint64_t* keys, int32_t* idx, int state_is_device,
+                    int first, int cand_split);
+/* keys / idx (in, out) become, per row, the k smallest (key, index) of
+ * themselves and a second list of the same shape and location (keys_b, idx_b:
+ * read only).  Both sorted as above; the two must not share a candidate index.
+ * Kernel name: profile_knn_merge (one wave per row, no atomics). */
+int karma_knn_merge(karma_ctx* ctx, uint64_t* keys, int32_t* idx,
+                    const uint64_t* keys_b, const int32_t* idx_b,
+                    int64_t nq, int k, int state_is_device);
+/* out_idx = idx and out_dist = the correctly rounded sqrt of the d2 whose bits
+ * a key holds (nq x k each, host or device); an empty slot comes out as
+ * (-1, +inf).  The state is not changed.  Kernel name: profile_knn_finish. */
+int karma_knn_finish(karma_ctx* ctx, const uint64_t* keys, const int32_t* idx, int64_t nq, int k, int state_is_device,
+                     int32_t* out_idx, double* out_dist, int out_is_device);
+/* The split a karma_knn_block call of nq query rows and nc candidate rows runs
+ * with for this cand_split: the clamped value, or for 0 the library's choice:
+ * the largest S <= 32 with ceil(nq / query_rows) * S blocks within what the
+ * device holds at once (compute units x resident blocks of the kernel with
+ * the smallest lists), clamped to the tiles.  ctx is needed for 0 only. */
+int karma_knn_block_split(karma_ctx* ctx, int64_t nq, int64_t nc, int cand_split, int* used);
+
 /* ---- shared-read graph ----------------------------------------------------- */
 /* A pair list: unique keys (a << 32 | b, a <= b) sorted ascending with int64
  * counts (and, for eq classes, the first emission position). */

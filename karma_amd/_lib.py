@@ -111,6 +111,11 @@ _SIGS = {
     "karma_kmer_row_totals": [_c_p, _c_p],
     "karma_knn_rows": [_c_p, _c_p, _i64, _i64, _i64, _i32, _i64, _i64, _i32, _c_p, _c_p, _i32],
     "karma_knn_tile": [ctypes.POINTER(ctypes.c_int)] * 4,
+    "karma_knn_block": [_c_p, _c_p, _i64, _i64, _i32, _c_p, _i64, _i64, _i32, _i64, _i64, _i32, _c_p, _c_p, _i32, _i32,
+                        _i32],
+    "karma_knn_merge": [_c_p, _c_p, _c_p, _c_p, _c_p, _i64, _i32, _i32],
+    "karma_knn_finish": [_c_p, _c_p, _c_p, _i64, _i32, _i32, _c_p, _c_p, _i32],
+    "karma_knn_block_split": [_c_p, _i64, _i64, _i32, ctypes.POINTER(ctypes.c_int)],
     "karma_graph_records": [_c_p, _c_p, _i64, _i64, _i32, _i32, _PP],
     "karma_graph_records_begin": [_c_p, _c_p, _i64, _i64, _i32, _i32, _PP],
     "karma_graph_records_end": [_c_p, _PP],
@@ -479,6 +484,15 @@ def knn_tile():
     v = [ctypes.c_int(0) for _ in range(4)]
     call("karma_knn_tile", *[ctypes.byref(x) for x in v])
     return tuple(x.value for x in v)
+
+
+def knn_block_split(ctx, nq, nc, cand_split=0):
+    """The candidate split a karma_knn_block call of these sizes runs with (karma_knn_block_split).
+    ctx may be None for an explicit cand_split >= 1."""
+    used = ctypes.c_int(0)
+    call("karma_knn_block_split", ctx.h if ctx is not None else None, int(nq), int(nc), int(cand_split),
+         ctypes.byref(used))
+    return used.value
 
 
 def merge_tile():

@@ -330,6 +330,60 @@ def native_step_on(comm, ops, overlap):
     return isinstance(comm, (SoloComm, RcclComm))
 
 
+def knn_sharded(comm, ctx, local, bounds, k, cand_split=0):
+    """Exact k nearest rows of a profile whose rows are sharded over the ranks
+    (engine.KnnState; the contract is in include/karma.h, karma_knn_block).
+
+    local: this rank's rows on the device (a DevBuf or a DeviceProfile of
+    n_loc x M); bounds: the world + 1 row bounds of the shards, in rank order
+    (ShardedBuild.bounds).  Returns (idx int32[n_loc, k], dist float64[n_loc,
+    k]), idx holding global row numbers: this rank's rows of what
+    engine.knn_rows gives on the gathered matrix, bit for bit.
+
+    A ring of `world` rounds: in round s a rank folds the block that began at
+    rank (rank + s) % world, with that rank's bound as the index base, into its
+    own lists, then hands the block it holds to rank - 1 (one alltoallv with a
+    single nonzero count, so SoloComm, HostComm and RcclComm all run it).
+    Every rank makes the same collectives in the same order, ranks without
+    rows included.  The transfers are synchronous: nothing overlaps the fold."""
+    from .engine import KnnState, _knn_source
+
+    world, rank = comm.world, comm.rank
+    b = [int(x) for x in np.asarray(bounds).reshape(-1)]
+    if len(b) != world + 1 or b[0] != 0 or any(hi < lo for lo, hi in zip(b, b[1:])):
+        raise ValueError(f"bounds must be {world + 1} ascending row bounds from 0, not {b}")
+    n_glob = b[-1]
+    k = int(k)
+    k_max = _lib.knn_tile()[3]
+    if k < 1 or k > min(n_glob, k_max):
+        raise ValueError(f"need 1 <= k <= min(n, {k_max}), not k = {k} with n = {n_glob}")
+    host, dptr, n_loc, M, _ = _knn_source(local)
+    if host is not None:
+        raise TypeError("the local rows must be on the device (a DevBuf or a DeviceProfile)")
+    if n_loc != b[rank + 1] - b[rank]:
+        raise ValueError(f"rank {rank} holds {n_loc} rows, its bounds say {b[rank + 1] - b[rank]}")
+    state = KnnState(ctx, n_loc, k)
+    mine = DevBuf(ctx, (n_loc, M), np.float64, _ptr=dptr, _owner=local)
+    held = mine
+    try:
+        for s in range(world):
+            origin = (rank + s) % world
+            rows = b[origin + 1] - b[origin]
+            state.update(mine, held.reshape(rows, M), b[origin], cand_split)
+            if s + 1 < world:
+                counts = np.zeros(world, np.int64)
+                counts[(rank - 1) % world] = held.size
+                got, _ = comm.alltoallv(held.reshape(held.size), counts)
+                if held is not mine:
+                    held.close()
+                held = got
+        return state.finish()
+    finally:
+        if held is not mine:
+            held.close()
+        state.close()
+
+
 class ShardedBuild:
     """k-mer profile + shared-read graph over contig/fragment shards."""
 
@@ -348,6 +402,7 @@ class ShardedBuild:
         native = native_step_on(comm, ops, overlap)
         self.ops = ops if ops is not None else (None if native else HipOps(ctx))
         self._prof = None
+        self._kept = None  # the newest kept step's profile (knn)
         # The local graph build (records -> pair list) shares nothing with the
         # k-mer profile: with overlap it runs from a worker thread on a second
         # context/stream while this thread drives the profile; every collective
@@ -410,6 +465,25 @@ class ShardedBuild:
             if not self.flagged:
                 raise ValueError("FlaggedRecords need a ShardedBuild(flagged=True)")
             records, n_records = records.ptr, records.n_records
+        stats = self._step(store, records, n_records, keep, sequential, count)
+        if keep:
+            self._kept = stats["profile"]
+        return stats
+
+    def knn(self, k, cand_split=0):
+        """The exact k nearest rows of the kept step's profile (run(keep=True))
+        over all ranks' rows: (idx int32[n_loc, k] global row numbers, dist
+        float64[n_loc, k]) of this rank's rows (knn_sharded).  A collective:
+        every rank calls it."""
+        k = int(k)
+        k_max = _lib.knn_tile()[3]
+        if k < 1 or k > min(self.n_glob, k_max):
+            raise ValueError(f"need 1 <= k <= min(n, {k_max}), not k = {k} with n = {self.n_glob}")
+        if self._kept is None:
+            raise ValueError("no kept step: call run(keep=True) first")
+        return knn_sharded(self.comm, self._ctx, self._kept, self.bounds, k, cand_split)
+
+    def _step(self, store, records, n_records, keep, sequential, count):
         if self.native is not None:
             return self.native.run(store, records, n_records, keep=keep, sequential=sequential, count=count,
                                    flagged=self.flagged)
@@ -550,7 +624,7 @@ class ShardedBuild:
         return stats
 
     def close(self):
-        self._prof = None
+        self._prof = self._kept = None
         if self.native is not None:
             self.native.close()
             self.native = None

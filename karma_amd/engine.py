@@ -367,6 +367,162 @@ def knn_rows(x, k, row_lo=0, row_hi=None, ctx=None, out_device=False):
     return idx, dist
 
 
+KNN_MAX_INDEX = (1 << 31) - 1  # cand_base + nc may reach it (include/karma.h, karma_knn_block)
+
+
+def _knn_k(k):
+    k = int(k)
+    k_max = _lib.knn_tile()[3]
+    if k < 1 or k > k_max:
+        raise ValueError(f"need 1 <= k <= {k_max}, not k = {k}")
+    return k
+
+
+class KnnState:
+    """Per-query neighbour lists that outlive a call (karma_knn_block; the
+    contract is in include/karma.h): nq rows of the k smallest (d2 bits,
+    index) seen so far, on the device.  update() folds one block of candidate
+    rows with a global index base into them, in any block order; merge() folds
+    another state of the same queries; finish() gives (idx, dist) as knn_rows
+    does.  No candidate index may be offered twice.  The buffers are allocated
+    at the first update."""
+
+    def __init__(self, ctx, nq, k):
+        nq = int(nq)
+        if nq < 0 or nq >= 1 << 31:
+            raise ValueError(f"need 0 <= nq < 2^31, not nq = {nq}")
+        self.ctx, self.nq, self.k = ctx, nq, _knn_k(k)
+        self.keys = self.idx = None
+        self.first = True  # nothing folded yet: the next update does not read the state
+        self.rows_seen = 0  # candidate rows offered so far
+        self.closed = False
+
+    def _buffers(self):
+        if self.keys is None:
+            self.keys = _lib.DevBuf(self.ctx, (self.nq, self.k), np.uint64)
+            self.idx = _lib.DevBuf(self.ctx, (self.nq, self.k), np.int32)
+
+    def _open(self):
+        if self.closed:
+            raise ValueError("KnnState is closed")
+
+    def update(self, q, c, cand_base, cand_split=0):
+        """Fold the candidate rows c (index of row r: cand_base + r) into the
+        lists of the query rows q.  q, c: a numpy array, a DevBuf or a
+        DeviceProfile of the same column count; q has the state's nq rows.
+        cand_split: 0 lets the library choose, S >= 1 runs S slices of the
+        candidate tiles side by side (the lists do not depend on it)."""
+        self._open()
+        qh, qd, nq, M, ldq = _knn_source(q)
+        ch, cd, nc, Mc, ldc = _knn_source(c)
+        cand_base, cand_split = int(cand_base), int(cand_split)
+        if nq != self.nq:
+            raise ValueError(f"the state holds {self.nq} query rows, not {nq}")
+        if M != Mc:
+            raise ValueError(f"queries and candidates must have the same columns, not {M} and {Mc}")
+        if cand_base < 0 or cand_base + nc > KNN_MAX_INDEX:
+            raise ValueError(f"need 0 <= cand_base and cand_base + nc <= 2^31 - 1, not {cand_base} + {nc}")
+        if cand_split < 0:
+            raise ValueError(f"cand_split must not be negative, not {cand_split}")
+        if self.nq and (nc or self.first):
+            self._buffers()
+            call("karma_knn_block", self.ctx.h, ctypes.c_void_p(qd) if qh is None else ptr(qh), nq, ldq,
+                 1 if qh is None else 0, ctypes.c_void_p(cd) if ch is None else ptr(ch), nc, ldc,
+                 1 if ch is None else 0, M, cand_base, self.k, ctypes.c_void_p(self.keys.ptr),
+                 ctypes.c_void_p(self.idx.ptr), 1, 1 if self.first else 0, cand_split)
+        self.first = False
+        self.rows_seen += nc
+
+    def merge(self, other):
+        """Fold another state of the same queries (same nq, k and context) into this one."""
+        self._open()
+        if not isinstance(other, KnnState):
+            raise TypeError(f"merge takes a KnnState, not {type(other).__name__}")
+        other._open()
+        if (other.nq, other.k) != (self.nq, self.k):
+            raise ValueError(f"the states differ: {self.nq} x {self.k} and {other.nq} x {other.k}")
+        if other is self:
+            raise ValueError("a state cannot be merged into itself (no index may be offered twice)")
+        if other.first:
+            return
+        if self.nq:
+            self._buffers()
+            if self.first:  # nothing here yet: the other's lists as they are
+                self.keys.copy_from_device(other.keys)
+                self.idx.copy_from_device(other.idx)
+            else:
+                call("karma_knn_merge", self.ctx.h, ctypes.c_void_p(self.keys.ptr), ctypes.c_void_p(self.idx.ptr),
+                     ctypes.c_void_p(other.keys.ptr), ctypes.c_void_p(other.idx.ptr), self.nq, self.k, 1)
+        self.first = False
+        self.rows_seen += other.rows_seen
+
+    def finish(self, out_device=False):
+        """(idx int32[nq, k], dist float64[nq, k]): numpy arrays, or DevBufs
+        with out_device=True.  Fewer than k candidate rows so far is an error."""
+        self._open()
+        if self.rows_seen < self.k:
+            raise ValueError(f"need 1 <= k <= the candidate rows offered, not k = {self.k} with {self.rows_seen} rows")
+        if out_device:
+            idx, dist = _lib.DevBuf(self.ctx, (self.nq, self.k), np.int32), \
+                _lib.DevBuf(self.ctx, (self.nq, self.k), np.float64)
+            pi, pd = ctypes.c_void_p(idx.ptr), ctypes.c_void_p(dist.ptr)
+        else:
+            idx, dist = np.empty((self.nq, self.k), np.int32), np.empty((self.nq, self.k), np.float64)
+            pi, pd = ptr(idx), ptr(dist)
+        if self.nq:
+            call("karma_knn_finish", self.ctx.h, ctypes.c_void_p(self.keys.ptr), ctypes.c_void_p(self.idx.ptr),
+                 self.nq, self.k, 1, pi, pd, 1 if out_device else 0)
+        return idx, dist
+
+    def close(self):
+        for b in (self.keys, self.idx):
+            if b is not None:
+                b.close()
+        self.keys = self.idx = None
+        self.closed = True
+
+
+def knn_blocked(x, k, block_rows, ctx=None):
+    """knn_rows(x, k) of a host matrix (a numpy array, a numpy.memmap) walked
+    in blocks of block_rows rows: one query block, one candidate block and the
+    query block's lists are on the device at a time, so x may be larger than
+    device memory.  Returns (idx int32[n, k], dist float64[n, k]), bit for bit
+    knn_rows' result."""
+    if not isinstance(x, np.ndarray):
+        raise TypeError(f"the matrix must be a host numpy array (or memmap), not {type(x).__name__}")
+    if x.dtype != np.float64:
+        raise TypeError(f"the matrix must be float64 (distances are defined on its bits), not {x.dtype}")
+    if x.ndim != 2:
+        raise ValueError(f"the matrix must have shape (n, M), not {x.shape}")
+    n = x.shape[0]
+    k, block_rows = int(k), int(block_rows)
+    k_max = _lib.knn_tile()[3]
+    if k < 1 or k > min(n, k_max):
+        raise ValueError(f"need 1 <= k <= min(n, {k_max}), not k = {k} with n = {n}")
+    if block_rows < 1:
+        raise ValueError(f"block_rows must be at least 1, not {block_rows}")
+    ctx = ctx or _lib.default_context()
+    idx, dist = np.empty((n, k), np.int32), np.empty((n, k), np.float64)
+    for lo in range(0, n, block_rows):
+        hi = min(n, lo + block_rows)
+        q = _lib.DevBuf.from_numpy(ctx, x[lo:hi])
+        state = KnnState(ctx, hi - lo, k)
+        try:
+            for clo in range(0, n, block_rows):
+                chi = min(n, clo + block_rows)
+                c = q if clo == lo else _lib.DevBuf.from_numpy(ctx, x[clo:chi])
+                try:
+                    state.update(q, c, clo)
+                finally:
+                    if c is not q:
+                        c.close()
+            idx[lo:hi], dist[lo:hi] = state.finish()
+        finally:
+            state.close()
+            q.close()
+    return idx, dist
+
+
 # ---------------------------------------------------------------------------
 # Graph
 # ---------------------------------------------------------------------------
