@@ -414,6 +414,14 @@ int karma_pairs_merge_runs(karma_ctx* ctx, const uint64_t* keys, const int64_t* 
  * elements of a run per block, window keys a block can stage in LDS, runs
  * merged in one ranking pass, and lanes per window-bound search. */
 int karma_merge_tile(int* tile, int* lds_keys, int* max_runs, int* search_group);
+/* The same for the deferred step's tail (karma_step_run with KARMA_STEP_DEFER:
+ * its merge and edge stage are kernels of their own).  Fills the first n of
+ * v[0..7]: merge tile elements, window keys a block can stage in LDS, the most
+ * runs whose searches run in lockstep, lanes per window-bound search, edge
+ * stage tile elements, the most runs (owners), and the most blocks the merge
+ * and the edge stage are launched with on ctx's device (both 0 when ctx is
+ * NULL: the constants alone need no device). */
+int karma_step_tail_tile(karma_ctx* ctx, int* v, int n);
 /* The exchange's wire format: n x {i64 key, i64 count} interleaved in device
  * memory.  _get_kc writes the list in it (stream-ordered, not waited for);
  * _merge_runs_kc merges received runs of it (at most 64 runs: without a host

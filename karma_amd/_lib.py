@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import types
 import weakref
 
 import numpy as np
@@ -158,6 +159,7 @@ _SIGS = {
     "karma_step_edges": [_c_p, _PP],
     "karma_step_newest_edges": [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _i64, _i32, _I64P, _c_p],
     "karma_step_destroy": [_c_p],
+    "karma_step_tail_tile": [_c_p, _c_p, _i32],
     "karma_synth_contig_lengths": [_u64, _i64, _i32, _i32, _c_p],
     "karma_synth_contig_bases": [_u64, _c_p, _i64, _i32, _c_p],
     "karma_synth_n_genes": [_u64, _i64, _i32, _I64P],
@@ -501,6 +503,16 @@ def merge_tile():
     v = [ctypes.c_int(0) for _ in range(4)]
     call("karma_merge_tile", *[ctypes.byref(x) for x in v])
     return tuple(x.value for x in v)
+
+
+def step_tail_tile(ctx=None):
+    """The deferred step's tail kernels' constants (karma_step_tail_tile): merge tile elements, staged window
+    keys per block, most runs searched in lockstep, lanes per bound search, edge stage tile elements, most
+    runs, and the most blocks of the merge and of the edge stage on ctx's device (0, 0 without a context)."""
+    v = np.zeros(8, np.int32)
+    call("karma_step_tail_tile", ctx.h if ctx is not None else None, ptr(v), 8)
+    return types.SimpleNamespace(MT=int(v[0]), MLDS=int(v[1]), MFAST=int(v[2]), MG=int(v[3]), ET=int(v[4]),
+                                 MAX_RUNS=int(v[5]), merge_blocks=int(v[6]), edge_blocks=int(v[7]))
 
 
 def dtype_code(dtype):

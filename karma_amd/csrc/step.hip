@@ -211,6 +211,8 @@ constexpr int kMT = 1024;       // tile elements (one round of tiles at the 8-ra
 constexpr int kMLds = 8192;     // staged window keys
 constexpr int kMFast = 8;       // up to this many runs: every element's searches run in lockstep
 constexpr int kMG = 16;         // lanes per bound search
+// the most blocks per CU the merge and the edge stage are launched with (deferred_tail)
+constexpr int kMergePerCu = 8, kEdgePerCu = 4;
 struct RunSrc {
     int nr, B, bw;
     int64_t b[kMaxRuns + 1];     // owner bounds (contig ids)
@@ -1240,8 +1242,8 @@ int deferred_tail(karma_step* s, const DeferredSchedule& sc, const StepStreams& 
         const int64_t tiles_cap = (cap + kMT - 1) / kMT + s->nranks;
         // a tile per block up to 8 blocks per CU (the tiles' searches are
         // dependent loads: more tiles in flight, not more tiles per block)
-        KARMA_LAUNCH(ctx, "merge_rank", step_merge_kernel, (int)std::min<int64_t>(tiles_cap, 8 * cu), 256, 0, mkeys,
-                     mcounts, v.dst, v.split_loc, rs, tl.mk.ptr, tl.mc.ptr, tl.mbad.ptr);
+        KARMA_LAUNCH(ctx, "merge_rank", step_merge_kernel, (int)std::min<int64_t>(tiles_cap, kMergePerCu * cu), 256, 0,
+                     mkeys, mcounts, v.dst, v.split_loc, rs, tl.mk.ptr, tl.mc.ptr, tl.mbad.ptr);
         lk = tl.mk.ptr;
         lc = tl.mc.ptr;
         mbad = tl.mbad.ptr;
@@ -1256,7 +1258,7 @@ int deferred_tail(karma_step* s, const DeferredSchedule& sc, const StepStreams& 
     // the edge stage's tiles are chains of dependent loads (keys, totals): up
     // to 4 blocks per CU take a tile each (one block per CU striding over 12
     // tiles at the 8-rank weak preview's 3.2M keys took 29 + 46 us)
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((cap + kET - 1) / kET, 4 * cu));
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((cap + kET - 1) / kET, kEdgePerCu * cu));
     KARMA_LAUNCH(ctx, "edge_count", step_edge_count_kernel, grid, kET, 0, lk, lc, n_dev, s->n_glob, tl.tot.ptr,
                  tl.tile_cnt.ptr, tl.est.ptr);
     // the owners' readset totals from every owner (fixed sizes: no host wait)
@@ -1571,6 +1573,14 @@ int karma_step_newest_edges(karma_step* s, uint32_t* a, uint32_t* b, int64_t* sh
     }
     if (totals) KARMA_HIP(hipMemcpyAsync(totals, tl.tot.ptr, s->n_glob * 8, kind, q));
     KARMA_HIP(hipStreamSynchronize(q));
+    return KARMA_OK;
+}
+
+int karma_step_tail_tile(karma_ctx* ctx, int* v, int n) {
+    KARMA_CHECK(v && n >= 0, KARMA_ERR_ARG, "karma_step_tail_tile: bad arguments");
+    const int cu = ctx ? ctx->cu_count : 0;
+    const int c[] = {kMT, kMLds, kMFast, kMG, kET, kMaxRuns, kMergePerCu * cu, kEdgePerCu * cu};
+    for (int i = 0; i < n && i < (int)(sizeof c / sizeof c[0]); ++i) v[i] = c[i];
     return KARMA_OK;
 }
 

@@ -22,6 +22,10 @@ Cases (--case):
                second build whose deferred steps fit; a third where only
                rank 0's batches hold a read for the general path; infos,
                newest profiles and kept results to npz
+  tail         a rank case of tests/step_tail_reference.py (--npz: every rank's
+               records per step, written by tests/test_gpu_step_tail.py): a
+               synchronous sizing step, two deferred dirtying steps, the deferred
+               step under test; newest edges, deferred flag and info to npz
   config4      BASELINE configs[3]: config 3 over W ranks (bench.py's exact
                strong workload); the union of outputs hashed with
                tests/digests.py (the parent compares with digests.json config3)
@@ -217,6 +221,39 @@ def defer_rank(group, rank, sizes, frags, seed):
         ctx.close()
 
 
+def tail_rank(group, rank, path):
+    """One rank of a tests/step_tail_reference.py rank case: a synchronous
+    step (sizes the slots), two deferred dirtying steps, the deferred step
+    under test; its newest edges, the deferred flag and the step's info."""
+    with np.load(path) as d:
+        bounds = d["bounds"]
+        steps = [np.ascontiguousarray(d[f"{k}{rank}"]) for k in ("sizing", "dirt0_", "dirt1_", "rec")]
+    n_glob, c_lo, n_loc = int(bounds[-1]), int(bounds[rank]), int(bounds[rank + 1] - bounds[rank])
+    ctx = _lib.Context(0)
+    comm = RcclComm(group, ctx)
+    try:
+        blob, offs, key_len = engine.synth_contigs(43, n_loc, 30, 40, 0, first=c_lo)
+        store = engine.ContigStore(ctx, blob, offs, key_len)
+        bufs = [dev_records(ctx, r) for r in steps]
+        build = ShardedBuild(ctx, comm, -1, n_glob, c_lo, n_loc)
+        try:
+            assert build.native is not None
+            for r, b in zip(steps, bufs):
+                build.run(store, b.ptr, len(r), count=False)
+            build.sync()
+            ne, dfr = build.native.newest_edges()
+            return dict(info=build.native.info(), deferred=np.array(dfr), a=ne.a, b=ne.b, s=ne.shared, w=ne.weight,
+                        tot=ne.totals)
+        finally:
+            build.close()
+            store.close()
+            for b in bufs:
+                b.close()
+    finally:
+        comm.close()
+        ctx.close()
+
+
 def config4_rank(group, rank):
     import digests as D
 
@@ -246,7 +283,8 @@ def config4_rank(group, rank):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=("collectives", "oracle", "defer", "config4"), required=True)
+    ap.add_argument("--case", choices=("collectives", "oracle", "defer", "config4", "tail"), required=True)
+    ap.add_argument("--npz", default="", help="tail case: the records of every rank and step")
     ap.add_argument("--world", type=int, default=3)
     ap.add_argument("--out", default=".")
     ap.add_argument("--sizes", default="")
@@ -273,6 +311,9 @@ def main():
         sizes = [int(x) for x in a.sizes.split(",")]
         parts = run_ranks(a.world, oracle_rank if a.case == "oracle" else defer_rank, sizes, a.frags, a.seed)
         for r, p in enumerate(parts):
+            np.savez(os.path.join(a.out, f"rank{r}.npz"), **p)
+    elif a.case == "tail":
+        for r, p in enumerate(run_ranks(a.world, tail_rank, a.npz)):
             np.savez(os.path.join(a.out, f"rank{r}.npz"), **p)
     else:
         import digests as D
