@@ -169,6 +169,13 @@ int karma_contigs_create(karma_ctx* ctx, const uint8_t* seq, const int64_t* offs
 int karma_contigs_destroy(karma_contigs* c);
 int karma_contigs_info(karma_contigs* c, int64_t* n, int64_t* total_bases, int64_t* exception_bases,
                        int64_t* packed_bytes);
+/* For tests: the store's arrays copied to the host (a null pointer skips one).
+ * packed and mask: one entry per 16 bases, every contig starting on a word
+ * (ceil(len / 16) words each, woff[n] in all); packed has the first base in
+ * bits 31:30, A C G T = 0 1 2 3 and every other or missing base 0; mask has
+ * bit 15 - j set when base j is none of A, C, G, T.  woff: n + 1 word offsets.
+ * has_exc: n flags, contig has such a base.  Synchronises the stream. */
+int karma_contigs_words(karma_contigs* c, uint32_t* packed, uint16_t* mask, int64_t* woff, uint8_t* has_exc);
 
 /* ---- k-mer profile (kmer.py:146-264) -------------------------------------- */
 typedef struct karma_kmer_plan karma_kmer_plan;
@@ -219,6 +226,21 @@ int karma_ctx_join(karma_ctx* ctx, void* side);
 int karma_ctx_set_side_headroom(karma_ctx* ctx, int blocks_per_cu);
 /* Number of k-mer occurrences per contig (0 => the all-zero row of kmer.py:250-258). */
 int karma_kmer_row_totals(karma_kmer_plan* p, int64_t* dst_host);
+/* For tests: the sizes the k-mer kernels are laid out by, the first n of:
+ * positions and packed words of a stage, zero words behind the store, contigs
+ * of the presence pass's first launch, waves per presence block and per
+ * profile block, the most columns and the largest ordinal space of the
+ * wave-per-contig profile, the most columns of a block's LDS histogram, the
+ * size of a row's quotient table, the contig length from which counters are
+ * u32, the column table's block size, the most blocks of the pack and of a
+ * presence launch.  No device call. */
+int karma_kmer_tile(int* v, int n);
+/* For tests: the kernel karma_kmer_profile launches for this plan: 0 one wave
+ * per contig with u16 counters, 1 the same with u32 counters, 2 one block per
+ * contig with its counts in LDS, 3 the same with a scratch row.  use_cap = 0:
+ * chosen on M (after finalize); 1: on the most columns the plan can have, as a
+ * step that leaves M on the device does.  No device call. */
+int karma_kmer_profile_path(karma_kmer_plan* p, int use_cap, int* path);
 
 /* ---- exact k nearest neighbours of matrix rows (the profile's kNN graph) ---- */
 /* x: row-major f64, n rows, m columns, row stride ld >= m (in doubles), on the

@@ -110,6 +110,9 @@ _SIGS = {
     "karma_ctx_join": [_c_p, _c_p],
     "karma_ctx_set_side_headroom": [_c_p, _i32],
     "karma_kmer_row_totals": [_c_p, _c_p],
+    "karma_kmer_tile": [_c_p, _i32],
+    "karma_contigs_words": [_c_p, _c_p, _c_p, _c_p, _c_p],
+    "karma_kmer_profile_path": [_c_p, _i32, ctypes.POINTER(ctypes.c_int)],
     "karma_knn_rows": [_c_p, _c_p, _i64, _i64, _i64, _i32, _i64, _i64, _i32, _c_p, _c_p, _i32],
     "karma_knn_tile": [ctypes.POINTER(ctypes.c_int)] * 4,
     "karma_knn_block": [_c_p, _c_p, _i64, _i64, _i32, _c_p, _i64, _i64, _i32, _i64, _i64, _i32, _c_p, _c_p, _i32, _i32,
@@ -513,6 +516,19 @@ def step_tail_tile(ctx=None):
     call("karma_step_tail_tile", ctx.h if ctx is not None else None, ptr(v), 8)
     return types.SimpleNamespace(MT=int(v[0]), MLDS=int(v[1]), MFAST=int(v[2]), MG=int(v[3]), ET=int(v[4]),
                                  MAX_RUNS=int(v[5]), merge_blocks=int(v[6]), edge_blocks=int(v[7]))
+
+
+def kmer_tile():
+    """The k-mer kernels' constants (karma_kmer_tile): positions and words of a stage, pad words behind the
+    store, contigs of the first presence launch, waves per presence and per profile block, the wave profile's
+    most columns and largest ordinal space, the most columns of an LDS histogram, the quotient table's size,
+    the length from which counters are u32, the column table's block, the pack and presence grid caps."""
+    v = np.zeros(14, np.int32)
+    call("karma_kmer_tile", ptr(v), 14)
+    return types.SimpleNamespace(STAGE=int(v[0]), STAGE_WORDS=int(v[1]), PAD_WORDS=int(v[2]), PREFIX=int(v[3]),
+                                 PRES_WAVES=int(v[4]), PROF_WAVES=int(v[5]), WAVE_MAX_M=int(v[6]),
+                                 WAVE_MAX_S=int(v[7]), LDS_COLS=int(v[8]), QUOT_TAB=int(v[9]), U16_LIMIT=int(v[10]),
+                                 COL_BLOCK=int(v[11]), PACK_GRID=int(v[12]), PRES_GRID=int(v[13]))
 
 
 def dtype_code(dtype):

@@ -105,6 +105,16 @@ int sort_unique_keys(karma_ctx* ctx, const uint64_t* src, int64_t n, DevArray<ui
 constexpr int kBlock = 256;
 constexpr int kPBlock = 512;  // profile: 8 waves share one LDS column table
 constexpr int kPadWords = 80;    // zero words after the store (stages may read past the last contig)
+// The sizes the kernels below are laid out by (karma_kmer_tile reports them).
+constexpr int kStagePos = 1024;                // contig positions a wave stages at a time
+constexpr int kStageWords = kStagePos / 16 + 1;  // their packed words: 64 and the one the last windows reach into
+constexpr int64_t kPresPrefix = 4096;          // contigs of the presence pass's first launch
+constexpr int kPackGridCap = 8192;             // most blocks of pack_kernel
+constexpr int kPresGridCap = 2048;             // most blocks of a presence launch
+constexpr uint32_t kWaveMaxS = 8192;           // largest ordinal space of the wave-per-contig profile
+constexpr int64_t kLdsCols = 144 * 1024 / 4;   // most columns of a block's LDS histogram
+constexpr uint32_t kQuotTab = 64;              // counts below it take count / len from the row's table
+constexpr int64_t kU16Limit = 65536;           // contigs shorter than this count in u16
 
 // ---------------------------------------------------------------- pack -------
 typedef unsigned int u32x4a __attribute__((ext_vector_type(4), aligned(4)));  // dword-aligned 16-byte load
@@ -266,7 +276,7 @@ __device__ __forceinline__ Window load_window(const uint32_t* packed, const uint
 template <typename Body>
 __device__ __forceinline__ void window_round(int64_t base, int64_t npos, bool excp, const uint32_t* wbuf,
                                              const uint16_t* mbuf, int lane, Body& body) {
-    const int64_t lim = min(npos, base + 1024);
+    const int64_t lim = min(npos, base + kStagePos);
     for (int64_t i = base + lane; i < lim; i += 64) {
         const int l = (int)(i - base), w = l >> 4;
         Window v;
@@ -291,18 +301,18 @@ struct Stage {
     __device__ __forceinline__ void load(const uint32_t* __restrict__ packed, const uint16_t* __restrict__ mask,
                                          bool excp, int64_t wb, int lane) {
         w = packed[wb + lane];
-        if (lane == 0) w64 = packed[wb + 64];
+        if (lane == 0) w64 = packed[wb + kStageWords - 1];
         if (excp) {
             m = mask[wb + lane];
-            if (lane == 0) m64 = mask[wb + 64];
+            if (lane == 0) m64 = mask[wb + kStageWords - 1];
         }
     }
     __device__ __forceinline__ void put(uint32_t* wbuf, uint16_t* mbuf, bool excp, int lane) const {
         wbuf[lane] = w;
-        if (lane == 0) wbuf[64] = w64;
+        if (lane == 0) wbuf[kStageWords - 1] = w64;
         if (excp) {
             mbuf[lane] = m;
-            if (lane == 0) mbuf[64] = m64;
+            if (lane == 0) mbuf[kStageWords - 1] = m64;
         }
     }
 };
@@ -316,7 +326,7 @@ __device__ __forceinline__ void for_each_window(const uint32_t* __restrict__ pac
                                                 const uint16_t* __restrict__ mask, bool excp, int64_t w0,
                                                 int64_t npos, uint32_t* wbuf, uint16_t* mbuf, int lane, Body body,
                                                 const Stage* first = nullptr) {
-    for (int64_t base = 0; base < npos; base += 1024) {
+    for (int64_t base = 0; base < npos; base += kStagePos) {
         Stage st;
         if (first && base == 0) st = *first;
         else st.load(packed, mask, excp, w0 + (base >> 4), lane);
@@ -617,7 +627,7 @@ __device__ __forceinline__ void count_clean(const Stage& first, const uint32_t* 
     const int64_t npos = L - kmin + 1;
     const int o = lane & 15;
     const uint32_t sh = 32u - 2u * (uint32_t)o;
-    for (int64_t b0 = 0; b0 < npos; b0 += 1024) {
+    for (int64_t b0 = 0; b0 < npos; b0 += kStagePos) {
         Stage st;
         if (b0 == 0) st = first;
         else st.load(packed, nullptr, false, w0 + (b0 >> 4), lane);
@@ -628,7 +638,7 @@ __device__ __forceinline__ void count_clean(const Stage& first, const uint32_t* 
         wave_lds_sync();
         const uint64_t* pw = pairs + (lane >> 4);
         const int64_t lim = npos - b0 - lane;  // position 64t + lane is valid iff 64t < lim
-        const int nt = (int)min<int64_t>(16, (npos - b0 + 63) >> 6);
+        const int nt = (int)min<int64_t>(kStagePos / 64, (npos - b0 + 63) >> 6);
 #pragma unroll 2
         for (int t = 0; t < nt; ++t) {
             if (64 * t < lim) {
@@ -668,8 +678,8 @@ __device__ __forceinline__ void write_row_wave(double* __restrict__ row, uint32_
     lut[lane] = lane ? (double)lane / len : 0.0;  // IEEE correctly rounded (kmer.py:120)
     wave_lds_sync();
     auto val = [&](uint32_t a) {
-        double v = lut[min(a, 63u)];
-        if (a >= 64u) v = (double)a / len;
+        double v = lut[min(a, kQuotTab - 1u)];
+        if (a >= kQuotTab) v = (double)a / len;
         return v;
     };
     if ((reinterpret_cast<uintptr_t>(row) & 15) == 0) {
@@ -1003,7 +1013,7 @@ int karma_contigs_create(karma_ctx* ctx, const uint8_t* seq, const int64_t* offs
     KARMA_HIP(hipMemsetAsync(stat.ptr, 0, 3 * sizeof(unsigned long long), ctx->stream));
     KARMA_HIP(hipMemsetAsync(c->exc_n.ptr, 0, sizeof(unsigned), ctx->stream));
     if (n) {
-        KARMA_LAUNCH(ctx, "pack_2bit", pack_kernel, grid_for(ceil_div(n, kBlock / 64), 8192), kBlock, 0, c->raw,
+        KARMA_LAUNCH(ctx, "pack_2bit", pack_kernel, grid_for(ceil_div(n, kBlock / 64), kPackGridCap), kBlock, 0, c->raw,
                      c->off, c->woff.ptr, n,
                      c->packed.ptr, c->mask.ptr, c->has_exc.ptr, stat.ptr, c->exc_list.ptr, c->exc_n.ptr);
         KARMA_LAUNCH(ctx, "zero_key", zero_key_kernel, ceil_div(n, 256), 256, 0, c->off, c->keylen, n, stat.ptr + 1,
@@ -1075,12 +1085,12 @@ int karma::kmer_plan_create(karma_ctx* ctx, karma_contigs* c, int kmode, const P
     if (c->n) {
         // phase A over a prefix, saturation test, phase B over the rest (only
         // contigs with exception bases once the ACGT ordinals are saturated)
-        const int64_t nA = std::min<int64_t>(c->n, 4096);
+        const int64_t nA = std::min<int64_t>(c->n, kPresPrefix);
         const size_t lds = p->nwords * 4 + (kBlock / 64) * 80 * (4 + 2);
         const bool p56 = kmode == KARMA_KMER_5P6;
         auto launch = [&](int64_t lo, int64_t hi, uint32_t n_can) -> int {
             if (hi <= lo) return KARMA_OK;
-            const int grid = grid_for(ceil_div(hi - lo, kBlock / 64), 2048);
+            const int grid = grid_for(ceil_div(hi - lo, kBlock / 64), kPresGridCap);
             if (p56)
                 KARMA_LAUNCH(ctx, "kmer_presence", presence_kernel<true>, grid, kBlock, lds, c->packed.ptr,
                              c->mask.ptr, c->has_exc.ptr, c->woff.ptr, c->off, c->raw, hi, kmode, (int)p->nwords,
@@ -1210,6 +1220,15 @@ int karma_kmer_plan_finalize_async(karma_kmer_plan* p) {
 static int profile_rows(karma_kmer_plan* p, int64_t lo, int64_t hi, double* out, int64_t ld, int out_is_device,
                         const int64_t* m_dev, int headroom = 0);
 
+// Which kernel writes a profile of M columns (the capacity kmer_m_cap when the
+// kernels read M on the device): the wave kernel with u16 or u32 counters, or
+// the block kernel with its histogram in LDS or in a scratch row.
+enum ProfilePath { kPathWave16 = 0, kPathWave32 = 1, kPathBlockLds = 2, kPathBlockScratch = 3 };
+static ProfilePath profile_path(const karma_kmer_plan* p, int64_t M) {
+    if (M <= kWaveMaxM && p->S <= kWaveMaxS) return p->store->max_len < kU16Limit ? kPathWave16 : kPathWave32;
+    return M <= kLdsCols ? kPathBlockLds : kPathBlockScratch;
+}
+
 namespace karma {
 // The column table without M's readback (karma_step's deferred steps): M is
 // written to m_out on the device (the caller's word) for the profile kernels;
@@ -1275,6 +1294,36 @@ int karma_kmer_columns(karma_kmer_plan* p, uint64_t* keys_host) {
     return KARMA_OK;
 }
 
+int karma_kmer_tile(int* v, int n) {
+    KARMA_CHECK(v && n >= 0, KARMA_ERR_ARG, "karma_kmer_tile: bad arguments");
+    const int c[] = {kStagePos, kStageWords, kPadWords, (int)kPresPrefix, kBlock / 64, kPBlock / 64, kWaveMaxM,
+                     (int)kWaveMaxS, (int)kLdsCols, (int)kQuotTab, (int)kU16Limit, kColBlock, kPackGridCap,
+                     kPresGridCap};
+    for (int i = 0; i < n && i < (int)(sizeof c / sizeof c[0]); ++i) v[i] = c[i];
+    return KARMA_OK;
+}
+
+int karma_contigs_words(karma_contigs* c, uint32_t* packed, uint16_t* mask, int64_t* woff, uint8_t* has_exc) {
+    KARMA_CHECK(c, KARMA_ERR_ARG, "null contigs");
+    karma_ctx* ctx = c->ctx;
+    KARMA_TRY(ctx_begin(ctx));
+    if (packed && c->words)
+        KARMA_HIP(hipMemcpyAsync(packed, c->packed.ptr, c->words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (mask && c->words)
+        KARMA_HIP(hipMemcpyAsync(mask, c->mask.ptr, c->words * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (woff) KARMA_HIP(hipMemcpyAsync(woff, c->woff.ptr, (c->n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (has_exc && c->n) KARMA_HIP(hipMemcpyAsync(has_exc, c->has_exc.ptr, c->n, hipMemcpyDeviceToHost, ctx->stream));
+    KARMA_HIP(hipStreamSynchronize(ctx->stream));
+    return KARMA_OK;
+}
+
+int karma_kmer_profile_path(karma_kmer_plan* p, int use_cap, int* path) {
+    KARMA_CHECK(p && p->store && path, KARMA_ERR_ARG, "karma_kmer_profile_path: bad arguments");
+    KARMA_CHECK(use_cap || p->M >= 0, KARMA_ERR_STATE, "karma_kmer_profile_path before finalize");
+    *path = (int)profile_path(p, use_cap ? kmer_m_cap(p) : p->M);
+    return KARMA_OK;
+}
+
 int karma_kmer_row_totals(karma_kmer_plan* p, int64_t* dst) {
     KARMA_CHECK(p, KARMA_ERR_ARG, "null plan");
     KARMA_TRY(ctx_begin(p->ctx));
@@ -1310,7 +1359,8 @@ static int profile_rows(karma_kmer_plan* p, int64_t lo, int64_t hi, double* out,
     const int64_t* const woff = c->woff.ptr + lo;
     const int64_t* const off = c->off + lo;
     const int32_t* const keylen = c->keylen + lo;
-    const bool wave = M <= kWaveMaxM && p->S <= 8192;
+    const ProfilePath path = profile_path(p, M);
+    const bool wave = path == kPathWave16 || path == kPathWave32;
     // row totals: with M == 0 every row is all-zero (kmer.py:250-258); the
     // block kernel adds to them; the wave kernel writes every row's total
     if (M == 0 || !wave) KARMA_HIP(hipMemsetAsync(row_tot, 0, n * 8, ctx->stream));
@@ -1335,7 +1385,7 @@ static int profile_rows(karma_kmer_plan* p, int64_t lo, int64_t hi, double* out,
         // one round of resident blocks, each wave striding over contigs; u16
         // counters when no contig reaches 2^16 bases (a count is <= L)
         const bool p56 = p->kmode == KARMA_KMER_5P6;
-        const bool c16 = c->max_len < 65536;
+        const bool c16 = path == kPathWave16;
         const int64_t t_pad = (tab_entries(p56, p->S) + 7) & ~7;
         const size_t lds = (size_t)t_pad * 2 + (kPBlock / 64) * (size_t)(hist_words(M, c16) + kProfWin) * 4;
 #define KARMA_WAVE_LAUNCH(P56, C16)                                                                              \
@@ -1356,7 +1406,7 @@ static int profile_rows(karma_kmer_plan* p, int64_t lo, int64_t hi, double* out,
         }
 #undef KARMA_WAVE_LAUNCH
     } else {
-        const bool lds_ok = M * 4 <= 144 * 1024;
+        const bool lds_ok = path == kPathBlockLds;
         const int grid = grid_for(n, lds_ok ? 4096 : 1024);
         DevArray<uint32_t> scratch;
         if (!lds_ok && (rc = scratch.alloc(ctx, (size_t)grid * M))) return rc;
@@ -1397,7 +1447,7 @@ int karma_kmer_profile_side(karma_kmer_plan* p, double* out_dev, int64_t ld, voi
     karma_ctx* ctx = p->ctx;
     KARMA_TRY(ctx_begin(ctx));
     // the general kernel past 36,864 columns allocates scratch: main stream
-    if (!side || (p->M > kWaveMaxM && p->M * 4 > 144 * 1024)) return karma_kmer_profile(p, out_dev, ld, 1);
+    if (!side || (p->M > kWaveMaxM && p->M > kLdsCols)) return karma_kmer_profile(p, out_dev, ld, 1);
     hipStream_t s = static_cast<hipStream_t>(side);
     KARMA_CHECK(p->fin_ev && p->M >= 0, KARMA_ERR_STATE, "karma_kmer_profile_side before finalize");
     if (ctx->mark_set) {

@@ -83,6 +83,17 @@ class ContigStore:
         call("karma_contigs_info", self.h, *[ctypes.byref(x) for x in v])
         return dict(n=v[0].value, total_bases=v[1].value, exception_bases=v[2].value, packed_bytes=v[3].value)
 
+    def words(self):
+        """The packed store on the host (karma_contigs_words): (packed uint32[W], mask uint16[W],
+        word offsets int64[n + 1], exception flag uint8[n])."""
+        woff = np.zeros(self.n + 1, np.int64)
+        call("karma_contigs_words", self.h, None, None, ptr(woff), None)
+        W = int(woff[-1])
+        packed, mask, has_exc = np.zeros(W, np.uint32), np.zeros(W, np.uint16), np.zeros(self.n, np.uint8)
+        call("karma_contigs_words", self.h, ptr(packed) if W else None, ptr(mask) if W else None, None,
+             ptr(has_exc) if self.n else None)
+        return packed, mask, woff, has_exc
+
     def close(self):
         if getattr(self, "h", None):
             _lib.load().karma_contigs_destroy(self.h)
@@ -149,6 +160,13 @@ class KmerPlan:
         keys = np.zeros(max(self.M, 1), dtype=np.uint64)
         call("karma_kmer_columns", self.h, ptr(keys))
         return keys[: self.M]
+
+    def profile_path(self, use_cap=False):
+        """The kernel the profile runs (karma_kmer_profile_path): 0 wave u16, 1 wave u32, 2 block with LDS
+        counts, 3 block with scratch rows; use_cap: chosen on the column capacity, as the deferred step does."""
+        v = ctypes.c_int(-1)
+        call("karma_kmer_profile_path", self.h, 1 if use_cap else 0, ctypes.byref(v))
+        return v.value
 
     def row_totals(self):
         out = np.zeros(max(self.store.n, 1), dtype=np.int64)
