@@ -344,6 +344,88 @@ int karma_knn_finish(karma_ctx* ctx, const uint64_t* keys, const int32_t* idx, i
  * the smallest lists), clamped to the tiles.  ctx is needed for 0 only. */
 int karma_knn_block_split(karma_ctx* ctx, int64_t nq, int64_t nc, int cand_split, int* used);
 
+/* ---- HDBSCAN: mutual-reachability spanning tree and cluster tree ------------- */
+/* x: row-major f64, n rows, m columns, row stride ld >= m (in doubles), on the
+ * host (x_is_device = 0: copied up) or the device.  Writes the exact minimum
+ * spanning tree of the complete mutual-reachability graph of the rows:
+ *
+ *   d2(i, j)   karma_knn_rows' definition exactly: the columns in order from
+ *              +0.0, t = x[i,c] - x[j,c]; acc = acc + t * t, no contraction.
+ *              Symmetric bit for bit.
+ *   core2(i)   the min_samples-th smallest (d2(i, j), j) over all j in [0, n),
+ *              row i itself counted: the last key of karma_knn_rows with
+ *              k = min_samples (scikit-learn's kneighbors(X, min_samples)[:, -1]).
+ *              core[i] is the correctly rounded sqrt(core2(i)).
+ *   mr2(i, j)  max(d2(i, j), core2(i), core2(j)).  All values are >= +0, so
+ *              the u64 bit patterns order them.
+ *   tree       the one minimum spanning tree of the complete graph under the
+ *              strict total order of the edge keys (mr2(i, j), lo, hi), lo =
+ *              min(i, j) < hi.  It does not depend on the algorithm: Kruskal
+ *              over all pairs sorted by that key gives these n - 1 edges, and
+ *              so does Prim with that comparison.
+ *   outputs    the n - 1 edges ascending by that key: a = lo, b = hi (int32),
+ *              w = the correctly rounded sqrt(mr2) (f64); core: f64[n].  The
+ *              order is by mr2, not by the rounded root.  Host or device
+ *              (out_is_device; all four alike).
+ *   limits     1 <= min_samples <= min(n, 64); 1 <= n < 2^31; m >= 0, where
+ *              m == 0 makes every d2 +0.  n == 1 writes core[0] = 0 and no
+ *              edge (a, b and w are then not looked at).
+ *
+ * Finite inputs only; a d2 that overflows to +inf from finite inputs is inside
+ * the contract and ties by index.  min_samples = 1 gives core 0: the plain
+ * Euclidean tree.
+ * KARMA_ERR_ARG with a message, before a device is looked for: a null pointer,
+ * min_samples out of range, ld < m, x, w or core off an 8-byte boundary (a, b:
+ * 4-byte), a byte size that overflows.  Boruvka rounds on karma_knn_rows' tile;
+ * the host reads one edge count per round and sorts the edges at the end.
+ * Kernel names in the timing table: profile_knn_block (the neighbour lists
+ * core2 is taken from), mst_core, and per round mst_nearest, mst_reduce (two
+ * passes), mst_hook (hook, pointer jumps, relabel). */
+int karma_mreach_mst(karma_ctx* ctx, const double* x, int64_t n, int64_t m, int64_t ld, int x_is_device,
+                     int min_samples, int32_t* a, int32_t* b, double* w, double* core, int out_is_device);
+/* The tile, for tests that place cases on its edges: query rows per block,
+ * candidate rows per step, columns staged at a time, and the most rounds any
+ * n takes (a round at least halves the components: ceil(log2 n)). */
+int karma_mst_tile(int* query_rows, int* cand_rows, int* col_panel, int* rounds_max);
+/* From a spanning tree's edges to HDBSCAN labels, on the host (no device, no
+ * context).  a, b, w: n - 1 edges in the order given, which must have
+ * non-decreasing w (karma_mreach_mst's output order); the order among equal
+ * weights is part of the input: it decides left and right below.
+ *
+ *   linkage    a union-find walks the edges in order; merge e makes node n + e
+ *              with left = find(a[e]), right = find(b[e]).
+ *   condensing breadth-first from the root, left before right, with lambda =
+ *              1 / w (+inf for w == 0).  A split whose two sides both hold at
+ *              least min_cluster_size points makes two new clusters, the left
+ *              one numbered first; otherwise the large side keeps its parent's
+ *              label and the points of a small side fall out at that lambda.
+ *   stability  of a label: sum of (lambda - lambda at the label's birth) * size
+ *              over what leaves it, in the order the condensing made it.
+ *   selection  excess of mass from the deepest label up: a label whose
+ *              children's summed stability is larger gives way to them (and
+ *              takes that sum), otherwise it is selected and everything below
+ *              it is not.  The root is a candidate only with
+ *              allow_single_cluster.
+ *   labels     selected clusters are numbered 0.. in ascending label; a point
+ *              belongs to the nearest selected label above it; noise is -1.
+ *              When the root is the one selected cluster, a point is a member
+ *              iff its lambda is >= the largest lambda among the root's
+ *              children.
+ *   prob       min(lambda_point, max_lambda(cluster)) / max_lambda(cluster);
+ *              1 where max_lambda is 0 or not finite; 0 for noise.
+ *
+ * This is scikit-learn 1.7's make_single_linkage followed by tree_to_labels
+ * with its defaults (excess of mass, epsilon 0, no maximum cluster size).
+ * n >= 1; n == 1 gives label -1, probability 0, zero clusters.
+ * min_cluster_size >= 2.  A cluster whose stability is not finite (zero-weight
+ * edges) is outside the contract.  KARMA_ERR_ARG, with nothing written: a null
+ * pointer, n or min_cluster_size out of range, a weight that is negative, NaN or
+ * below the one before it, an endpoint outside [0, n), an edge joining two
+ * points that are joined already. */
+int karma_hdbscan_tree(int64_t n, const int32_t* a, const int32_t* b, const double* w,
+                       int min_cluster_size, int allow_single_cluster,
+                       int32_t* labels, double* prob, int32_t* n_clusters);
+
 /* ---- shared-read graph ----------------------------------------------------- */
 /* A pair list: unique keys (a << 32 | b, a <= b) sorted ascending with int64
  * counts (and, for eq classes, the first emission position). */

@@ -120,6 +120,9 @@ _SIGS = {
     "karma_knn_merge": [_c_p, _c_p, _c_p, _c_p, _c_p, _i64, _i32, _i32],
     "karma_knn_finish": [_c_p, _c_p, _c_p, _i64, _i32, _i32, _c_p, _c_p, _i32],
     "karma_knn_block_split": [_c_p, _i64, _i64, _i32, ctypes.POINTER(ctypes.c_int)],
+    "karma_mreach_mst": [_c_p, _c_p, _i64, _i64, _i64, _i32, _i32, _c_p, _c_p, _c_p, _c_p, _i32],
+    "karma_mst_tile": [ctypes.POINTER(ctypes.c_int)] * 4,
+    "karma_hdbscan_tree": [_i64, _c_p, _c_p, _c_p, _i32, _i32, _c_p, _c_p, ctypes.POINTER(ctypes.c_int32)],
     "karma_graph_records": [_c_p, _c_p, _i64, _i64, _i32, _i32, _PP],
     "karma_graph_records_begin": [_c_p, _c_p, _i64, _i64, _i32, _i32, _PP],
     "karma_graph_records_end": [_c_p, _PP],
@@ -488,6 +491,13 @@ def knn_tile():
     """(query rows per block, candidate rows per step, columns staged at a time, largest k) of karma_knn_rows."""
     v = [ctypes.c_int(0) for _ in range(4)]
     call("karma_knn_tile", *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def mst_tile():
+    """(query rows per block, candidate rows per step, columns staged at a time, most rounds) of karma_mreach_mst."""
+    v = [ctypes.c_int(0) for _ in range(4)]
+    call("karma_mst_tile", *[ctypes.byref(x) for x in v])
     return tuple(x.value for x in v)
 
 

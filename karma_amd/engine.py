@@ -385,6 +385,89 @@ def knn_rows(x, k, row_lo=0, row_hi=None, ctx=None, out_device=False):
     return idx, dist
 
 
+def _mst_min_samples(min_samples, n):
+    min_samples = int(min_samples)
+    k_max = _lib.knn_tile()[3]
+    if n < 1:
+        raise ValueError("the matrix must have at least one row")
+    if min_samples < 1 or min_samples > min(n, k_max):
+        raise ValueError(f"need 1 <= min_samples <= min(n, {k_max}), not min_samples = {min_samples} with n = {n}")
+    return min_samples
+
+
+def mreach_mst(x, min_samples, ctx=None):
+    """The exact minimum spanning tree of the mutual-reachability graph of the
+    rows of the float64 matrix x (n, M) (karma_mreach_mst; the contract is in
+    include/karma.h): d2 as knn_rows defines it, core2(i) the min_samples-th
+    smallest (d2(i, j), j) with row i counted, mr2 = max(d2, core2(i),
+    core2(j)), and the one tree under the order (mr2, lo, hi).  x: what
+    knn_rows accepts.  Returns (a int32[n-1], b int32[n-1], w float64[n-1],
+    core float64[n]): the edges ascending by that key, a < b, w = sqrt(mr2),
+    core = sqrt(core2)."""
+    host, dptr, n, M, ld = _knn_source(x)
+    min_samples = _mst_min_samples(min_samples, n)
+    if ctx is None:
+        ctx = x.ctx if host is None else _lib.default_context()
+    a, b = np.empty(n - 1, np.int32), np.empty(n - 1, np.int32)
+    w, core = np.empty(n - 1, np.float64), np.empty(n, np.float64)
+    src = ctypes.c_void_p(dptr) if host is None else ptr(host)
+    call("karma_mreach_mst", ctx.h, src, n, M, ld, 1 if host is None else 0, min_samples, ptr(a), ptr(b), ptr(w),
+         ptr(core), 0)
+    return a, b, w, core
+
+
+def _min_cluster_size(min_cluster_size):
+    min_cluster_size = int(min_cluster_size)
+    if min_cluster_size < 2:
+        raise ValueError(f"need min_cluster_size >= 2, not {min_cluster_size}")
+    return min_cluster_size
+
+
+def hdbscan_tree(a, b, w, n, min_cluster_size, allow_single_cluster=False):
+    """HDBSCAN's labels from a spanning tree's edges, on the host
+    (karma_hdbscan_tree; include/karma.h): single linkage of the n - 1 edges in
+    the order given (w must not decrease), the condensed tree, excess of mass,
+    labels.  Returns (labels int32[n], probabilities float64[n]); noise is -1."""
+    n = int(n)
+    min_cluster_size = _min_cluster_size(min_cluster_size)
+    if n < 1:
+        raise ValueError("need n >= 1")
+    a = np.ascontiguousarray(a, np.int32)
+    b = np.ascontiguousarray(b, np.int32)
+    w = np.ascontiguousarray(w, np.float64)
+    if not a.shape == b.shape == w.shape == (n - 1,):
+        raise ValueError(f"a, b and w must each hold n - 1 = {n - 1} edges, not {a.shape}, {b.shape}, {w.shape}")
+    labels, prob = np.empty(n, np.int32), np.empty(n, np.float64)
+    count = ctypes.c_int32(0)
+    call("karma_hdbscan_tree", n, ptr(a), ptr(b), ptr(w), min_cluster_size, 1 if allow_single_cluster else 0,
+         ptr(labels), ptr(prob), ctypes.byref(count))
+    return labels, prob
+
+
+class HdbscanResult:
+    """What engine.hdbscan returns: labels_ (int32, noise -1) and
+    probabilities_ (float64), as a fitted clusterer's attributes are named."""
+
+    def __init__(self, labels, probabilities):
+        self.labels_ = labels
+        self.probabilities_ = probabilities
+
+
+def hdbscan(x, min_cluster_size=5, min_samples=None, allow_single_cluster=False, ctx=None):
+    """HDBSCAN of the rows of the float64 matrix x (n, M): the exact
+    mutual-reachability spanning tree on the device (mreach_mst) and the
+    cluster tree on the host (hdbscan_tree).  min_samples=None means
+    min_cluster_size; a point counts among its own neighbours, as in
+    scikit-learn.  Every bit of the result is defined by include/karma.h; it is
+    not claimed to equal the `hdbscan` package's labels (its default tree is
+    approximate and its tie order its own)."""
+    min_cluster_size = _min_cluster_size(min_cluster_size)
+    host, _, n, _, _ = _knn_source(x)
+    min_samples = _mst_min_samples(min_cluster_size if min_samples is None else min_samples, n)
+    a, b, w, _ = mreach_mst(x, min_samples, ctx=ctx)
+    return HdbscanResult(*hdbscan_tree(a, b, w, n, min_cluster_size, allow_single_cluster))
+
+
 KNN_MAX_INDEX = (1 << 31) - 1  # cand_base + nc may reach it (include/karma.h, karma_knn_block)
 
 

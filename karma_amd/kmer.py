@@ -131,7 +131,7 @@ class KmerClustering:
             fh.write("\t".join(kwargs.keys()) + "\n")
             fh.write("\t".join(str(v) for v in kwargs.values()) + "\n")
 
-    def run(self, neighbors, components, dist, r_state, min_cluster_size, device_knn=False):
+    def run(self, neighbors, components, dist, r_state, min_cluster_size, device_knn=False, device_hdbscan=False):
         """kmer.py:274-325.  The profile is computed on the GPU; UMAP/HDBSCAN
         are the reference's third-party dependencies and must be importable.
 
@@ -139,7 +139,15 @@ class KmerClustering:
         search UMAP starts with runs on the device too (kmer_knn) and is handed
         to umap.UMAP as precomputed_knn=(idx, dist), where the installed
         umap-learn has that parameter; where it has not (the reference pins
-        0.3.9), a warning is logged and UMAP searches by itself."""
+        0.3.9), a warning is logged and UMAP searches by itself.
+
+        device_hdbscan (an addition; default off: nothing changes): the
+        clustering of the embedding is engine.hdbscan (the exact
+        mutual-reachability spanning tree on the device, the cluster tree on
+        the host; include/karma.h) instead of the `hdbscan` package, which is
+        then not imported and need not be installed.  Its labels are defined
+        bit for bit by the library's contract and are not claimed to equal the
+        package's."""
         if os.path.isfile(self.output_file):
             logger.info(f"Read from previous calculation: {self.output_file}")
             self.__read_clusters()
@@ -151,12 +159,19 @@ class KmerClustering:
                 knn = (knn_idx, knn_dist)
             else:
                 kmer_profile = self.__calc_kmer_profile()
-            try:
-                import hdbscan
-                import umap
-            except ImportError as e:
-                raise ImportError("KmerClustering.run needs umap-learn and hdbscan (the reference's clustering "
-                                  "dependencies); the k-mer profile itself does not") from e
+            if device_hdbscan:
+                try:
+                    import umap
+                except ImportError as e:
+                    raise ImportError("KmerClustering.run(device_hdbscan=True) needs umap-learn; the k-mer profile "
+                                      "and the clustering do not") from e
+            else:
+                try:
+                    import hdbscan
+                    import umap
+                except ImportError as e:
+                    raise ImportError("KmerClustering.run needs umap-learn and hdbscan (the reference's clustering "
+                                      "dependencies); the k-mer profile itself does not") from e
             logger.info("Dimension reduction with UMAP.")
             umap_args = dict(n_neighbors=neighbors, n_components=components, min_dist=dist, random_state=r_state)
             if knn is not None:
@@ -166,7 +181,13 @@ class KmerClustering:
                     logger.warning("This umap-learn takes no precomputed_knn: UMAP searches the neighbours itself.")
             reduced = umap.UMAP(**umap_args).fit_transform(kmer_profile)
             logger.info(f"Perform clustering with HDBSCAN. (min_cluster_size: {min_cluster_size})")
-            if min_cluster_size == 1:
+            if device_hdbscan:
+                embedding = np.ascontiguousarray(reduced, dtype=np.float64)
+                if min_cluster_size == 1:
+                    clusterer = engine.hdbscan(embedding, min_cluster_size=5, allow_single_cluster=True)
+                else:
+                    clusterer = engine.hdbscan(embedding, min_cluster_size=min_cluster_size)
+            elif min_cluster_size == 1:
                 clusterer = hdbscan.HDBSCAN(allow_single_cluster=True).fit(reduced)
             else:
                 clusterer = hdbscan.HDBSCAN(min_cluster_size=min_cluster_size).fit(reduced)
