@@ -426,6 +426,129 @@ int karma_hdbscan_tree(int64_t n, const int32_t* a, const int32_t* b, const doub
                        int min_cluster_size, int allow_single_cluster,
                        int32_t* labels, double* prob, int32_t* n_clusters);
 
+/* ---- UMAP: fuzzy neighbour graph and layout ------------------------------------ */
+/* The step between the neighbour lists and HDBSCAN.  Every output bit is
+ * defined here; equality with umap-learn's coordinates is not claimed (its
+ * layout is a racy parallel SGD with its own generator).
+ *
+ *   kexp(x)   x = min(max(x, -745.0), 709.0); n = rint(x * LOG2E);
+ *             r = (x - n * LN2_HI) - n * LN2_LO; p = 1/13!; then for d = 12!,
+ *             11!, ..., 1!, 0!: p = p * r + 1.0 / d (the correctly rounded
+ *             quotients); h = floor(n * 0.5);
+ *             kexp = ldexp(ldexp(p, (int)h), (int)(n - h)).
+ *   klog(x)   x > 0 finite: (m, e) = frexp(x); if m < 0.7071067811865476:
+ *             m = m * 2.0, e = e - 1; f = m - 1.0; s = f / (2.0 + f); z = s * s;
+ *             p = 1/23; then for d = 21, 19, ..., 3, 1: p = p * z + 1.0 / d;
+ *             klog = e * LN2_HI + ((2.0 * s) * p + e * LN2_LO).
+ *   kpow(x, b) = kexp(b * klog(x)), x > 0.
+ *   LOG2E = 1.4426950408889634, LN2_HI = 6.93147180369123816490e-01,
+ *   LN2_LO = 1.90821492927058770002e-10.  Every step is one IEEE f64 + - * /,
+ *   a comparison, rint, floor, frexp or ldexp; no contraction (csrc/umap_math.h).
+ *   kexp is within 2.2e-16 of exp, klog within 4.4e-16 of log (relative).
+ *
+ * karma_umap_graph: the fuzzy simplicial set of neighbour lists idx (int32) and
+ * dist (f64), n x k row-major as karma_knn_rows / karma_knn_finish write them,
+ * on the host (in_is_device = 0: copied up) or the device.
+ *
+ *   rho(i)    the first dist[i, j] > 0 in list order, 0 if there is none
+ *             (umap's local_connectivity = 1).
+ *   sigma(i)  umap's smooth_knn_dist bisection with target = log2((double)k):
+ *             lo = 0, hi = +inf, mid = 1; at most 64 times: psum from +0.0 over
+ *             the entries j = 0 .. k - 1 in order with idx[i, j] != i, with
+ *             d = dist[i, j] - rho(i): psum = psum + (d > 0 ? kexp(-(d / mid))
+ *             : 1.0); stop if |psum - target| < 1e-5; else if psum > target:
+ *             hi = mid, mid = (lo + hi) / 2.0; else lo = mid, mid = mid * 2.0
+ *             while hi is +inf, otherwise (lo + hi) / 2.0.  Then sigma(i) =
+ *             max(mid, 1e-3 * mean): the row's in-order sum of its k distances
+ *             / k where rho(i) > 0, otherwise the global mean: the row sums
+ *             added in row order from +0.0, / (double)(n * k).
+ *   A[i, c]   for an entry with c = idx[i, j] != i and d = dist - rho(i): 1.0
+ *             if d <= 0 or sigma(i) == 0, otherwise kexp(-(d / sigma(i))).
+ *             Entries naming the row itself are dropped.
+ *   w(i, c)   with p = A[i, c], q = A[c, i], each 0 where absent:
+ *             (p + q) - p * q (umap's set_op_mix_ratio = 1): bit-symmetric.
+ *             Entries with w == 0 are dropped.
+ *   outputs   CSR: indptr int64[n + 1]; indices int32[nnz], each row ascending
+ *             by column; weights f64[nnz]; *nnz (always a host word).  The
+ *             result is a sorted set: it does not depend on the algorithm.
+ *             indices and weights hold cap >= 2 n k entries (the bound of nnz).
+ *             sigma, rho: f64[n], optional (null: not written).  Outputs on the
+ *             host or the device (out_is_device; all alike).
+ *   limits    2 <= k <= min(n, 64); 2 <= n < 2^31; 2 n k < 2^32.  A list must
+ *             not name a row twice (karma_knn_rows' never do).
+ *
+ * KARMA_ERR_ARG with a message, before a device is looked for: a null pointer,
+ * n or k out of range, cap < 2 n k, misalignment (f64 / int64: 8 bytes, int32:
+ * 4), a byte size that overflows, a host list naming a row outside [0, n).  A
+ * device list naming such a row is found by the first kernel: KARMA_ERR_ARG,
+ * nothing indexed with it.  Kernel name in the timing table: umap_graph (rows,
+ * sigma, entries, indptr, gather) around one radix sort of 2 n k keys. */
+int karma_umap_graph(karma_ctx* ctx, const int32_t* idx, const double* dist, int64_t n, int k, int in_is_device,
+                     int64_t* indptr, int32_t* indices, double* weights, int64_t cap, int64_t* nnz,
+                     double* sigma, double* rho, int out_is_device);
+/* Rows (vertices) per block of the graph's and the layout's per-row kernels,
+ * for tests that place cases on block edges. */
+int karma_umap_tile(int* rows_per_block);
+/* karma_umap_layout: the layout of a symmetric CSR graph (karma_umap_graph's
+ * output; host or device, graph_is_device) in gather form.  y: f64 n x dim
+ * row-major, in and out, host or device (y_is_device).
+ *
+ *   start     init != 0: y is first filled with y[i, c] = -10.0 + 20.0 *
+ *             ((splitmix64(seed + (i * dim + c + 1) * 0x9E3779B97F4A7C15) >> 11)
+ *             * 2^-53) (umap's init="random"); splitmix64(z): z = (z ^ z >> 30)
+ *             * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *             z ^ z >> 31 (u64).  init == 0: the caller's y.
+ *   schedule  per directed CSR entry e (row i, column j, weight w), wmax the
+ *             largest weight: active iff w >= wmax / (double)n_epochs (umap's
+ *             pruning; an inactive entry never fires but keeps its number e);
+ *             eps = wmax / w; eons = eps; epns = eps / (double)R; eonns = epns;
+ *             a u32 counter t_e = 0.  R = negative_sample_rate; R == 0: no
+ *             negatives.
+ *   epoch     ep = 0 .. n_epochs - 1, alpha = initial_alpha * (1.0 -
+ *             (double)ep / (double)n_epochs).  For every vertex i independently:
+ *             cur = Y_old[i]; for each active entry of row i in CSR order with
+ *             eons <= (double)ep:
+ *               attract  o = Y_old[j]; df[c] = cur[c] - o[c]; d2 = the in-order
+ *                        sum from +0.0 of df[c] * df[c]; if d2 > 0: pb =
+ *                        kpow(d2, b); g = ((-2.0 * a * b) * (pb / d2)) / (a * pb
+ *                        + 1.0); cur[c] = cur[c] + clip4(g * df[c]) * alpha,
+ *                        clip4 clamping to [-4, 4].
+ *               eons = eons + eps; nneg = (int)(((double)ep - eonns) / epns).
+ *               repel    nneg times: kk = splitmix64((seed ^ (e *
+ *                        0xD1342543DE82EF95)) + (t_e + 1) * 0x9E3779B97F4A7C15)
+ *                        mod n (u64); t_e += 1; o = Y_old[kk]; df, d2 as above;
+ *                        if d2 > 0: g = (2.0 * gamma * b) / ((0.001 + d2) * (a *
+ *                        kpow(d2, b) + 1.0)) and the same update; d2 == 0 (kk ==
+ *                        i among others): no move.
+ *               eonns = eonns + (double)nneg * epns.
+ *             Y_new[i] = cur.  Then the buffers swap.
+ *
+ * A vertex moves only through its own row; the graph is symmetric, so the entry
+ * (j, i) moves j by its own schedule (umap's move_other).  Own coordinates are
+ * live, everyone else's are those of the epoch's start: no race, no float
+ * atomic, and the result does not depend on block shape or launch order.
+ * limits: 1 <= dim <= 16; n_epochs >= 1; R >= 0; 2 <= n < 2^31; a, b, gamma,
+ * initial_alpha finite; weights finite and > 0.
+ * KARMA_ERR_ARG with a message: a null pointer, a range above, misalignment, a
+ * byte size that overflows, indptr not starting at 0, decreasing or not ending
+ * at nnz, a column outside [0, n), a bad weight -- for a host graph before a
+ * device is looked for, for a device graph by the first kernel, before anything
+ * is indexed with it.  One launch per epoch and no host wait between them; a
+ * hub's row is walked by the one thread that owns it.  Kernel name in the
+ * timing table: umap_layout. */
+int karma_umap_layout(karma_ctx* ctx, const int64_t* indptr, const int32_t* indices, const double* weights,
+                      int64_t n, int64_t nnz, int graph_is_device, int dim, double a, double b, int n_epochs,
+                      int negative_sample_rate, double gamma, double initial_alpha, uint64_t seed, int init,
+                      double* y, int y_is_device);
+/* umap's find_ab_params on the host (no device, no context): the least-squares
+ * fit of 1 / (1 + a x^(2b)) on the 300 points of linspace(0, 3 spread, 300) to
+ * 1 for x < min_dist, else exp(-(x - min_dist) / spread), by Levenberg-Marquardt
+ * from a = b = 1.  Agrees with scipy's curve_fit to its tolerances; a and b are
+ * inputs of the layout, whose bit contract does not rest on this fit.
+ * KARMA_ERR_ARG: a null pointer, spread not finite and > 0, min_dist not finite
+ * and >= 0. */
+int karma_umap_ab(double spread, double min_dist, double* a, double* b);
+
 /* ---- shared-read graph ----------------------------------------------------- */
 /* A pair list: unique keys (a << 32 | b, a <= b) sorted ascending with int64
  * counts (and, for eq classes, the first emission position). */

@@ -123,6 +123,12 @@ _SIGS = {
     "karma_mreach_mst": [_c_p, _c_p, _i64, _i64, _i64, _i32, _i32, _c_p, _c_p, _c_p, _c_p, _i32],
     "karma_mst_tile": [ctypes.POINTER(ctypes.c_int)] * 4,
     "karma_hdbscan_tree": [_i64, _c_p, _c_p, _c_p, _i32, _i32, _c_p, _c_p, ctypes.POINTER(ctypes.c_int32)],
+    "karma_umap_graph": [_c_p, _c_p, _c_p, _i64, _i32, _i32, _c_p, _c_p, _c_p, _i64, _I64P, _c_p, _c_p, _i32],
+    "karma_umap_tile": [ctypes.POINTER(ctypes.c_int)],
+    "karma_umap_layout": [_c_p, _c_p, _c_p, _c_p, _i64, _i64, _i32, _i32, ctypes.c_double, ctypes.c_double, _i32,
+                          _i32, ctypes.c_double, ctypes.c_double, _u64, _i32, _c_p, _i32],
+    "karma_umap_ab": [ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
+                      ctypes.POINTER(ctypes.c_double)],
     "karma_graph_records": [_c_p, _c_p, _i64, _i64, _i32, _i32, _PP],
     "karma_graph_records_begin": [_c_p, _c_p, _i64, _i64, _i32, _i32, _PP],
     "karma_graph_records_end": [_c_p, _PP],
@@ -499,6 +505,13 @@ def mst_tile():
     v = [ctypes.c_int(0) for _ in range(4)]
     call("karma_mst_tile", *[ctypes.byref(x) for x in v])
     return tuple(x.value for x in v)
+
+
+def umap_tile():
+    """Rows (vertices) per block of the UMAP graph's and layout's per-row kernels (karma_umap_tile)."""
+    v = ctypes.c_int(0)
+    call("karma_umap_tile", ctypes.byref(v))
+    return v.value
 
 
 def knn_block_split(ctx, nq, nc, cand_split=0):

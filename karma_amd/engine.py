@@ -468,6 +468,168 @@ def hdbscan(x, min_cluster_size=5, min_samples=None, allow_single_cluster=False,
     return HdbscanResult(*hdbscan_tree(a, b, w, n, min_cluster_size, allow_single_cluster))
 
 
+def _on_device(*arrays):
+    return all(isinstance(a, _lib.DevBuf) for a in arrays)
+
+
+def _dev_or_host(a, dtype):
+    """(argument for the library, the object that keeps it alive)."""
+    if isinstance(a, _lib.DevBuf):
+        if a.dtype != np.dtype(dtype):
+            raise TypeError(f"a device array of {a.dtype} where {np.dtype(dtype)} is needed")
+        if a.ptr is None:
+            raise ValueError("DevBuf is closed")
+        return ctypes.c_void_p(a.ptr), a
+    h = np.ascontiguousarray(a, dtype=dtype)
+    return ptr(h), h
+
+
+def umap_graph(idx, dist, ctx=None, out_device=False, with_sigma=False):
+    """UMAP's fuzzy simplicial set of exact neighbour lists (karma_umap_graph;
+    the contract is in include/karma.h): idx int32[n, k] and dist float64[n, k]
+    as knn_rows gives them, both numpy arrays or both DevBufs.  Returns the
+    symmetric graph in CSR, (indptr int64[n+1], indices int32[nnz], weights
+    float64[nnz]), each row ascending by column: numpy arrays, or DevBufs with
+    out_device=True.  with_sigma=True appends (sigma, rho), float64[n] each.
+    2 <= k <= min(n, 64)."""
+    device = _on_device(idx, dist)
+    if not device and (isinstance(idx, _lib.DevBuf) or isinstance(dist, _lib.DevBuf)):
+        raise TypeError("idx and dist must both be numpy arrays or both be DevBufs")
+    shape = tuple(idx.shape) if device else np.shape(idx)
+    if len(shape) != 2 or tuple(dist.shape if device else np.shape(dist)) != shape:
+        raise ValueError("idx and dist must have the same shape (n, k)")
+    n, k = shape
+    k_max = _lib.knn_tile()[3]
+    if n < 2 or k < 2 or k > min(n, k_max):
+        raise ValueError(f"need n >= 2 and 2 <= k <= min(n, {k_max}), not n = {n}, k = {k}")
+    if ctx is None:
+        ctx = idx.ctx if device else _lib.default_context()
+    pi, keep_i = _dev_or_host(idx, np.int32)
+    pd, keep_d = _dev_or_host(dist, np.float64)
+    cap = 2 * n * k
+    nnz = ctypes.c_int64(0)
+
+    def make(count, dtype):
+        return _lib.DevBuf(ctx, (count,), dtype) if out_device else np.empty(count, dtype)
+
+    def arg(buf):
+        return ctypes.c_void_p(buf.ptr) if out_device else ptr(buf)
+
+    indptr, indices, weights = make(n + 1, np.int64), make(cap, np.int32), make(cap, np.float64)
+    sigma, rho = (make(n, np.float64), make(n, np.float64)) if with_sigma else (None, None)
+    call("karma_umap_graph", ctx.h, pi, pd, n, k, 1 if device else 0, arg(indptr), arg(indices), arg(weights), cap,
+         ctypes.byref(nnz), arg(sigma) if with_sigma else None, arg(rho) if with_sigma else None,
+         1 if out_device else 0)
+    if out_device:
+        indices, weights = indices.view(0, nnz.value), weights.view(0, nnz.value)
+    else:
+        indices, weights = indices[:nnz.value].copy(), weights[:nnz.value].copy()
+    return (indptr, indices, weights, sigma, rho) if with_sigma else (indptr, indices, weights)
+
+
+def umap_ab(spread=1.0, min_dist=0.1):
+    """umap's find_ab_params (karma_umap_ab, on the host: no device needed):
+    (a, b) of the curve 1 / (1 + a x^(2b)) fitted to the membership curve of
+    (spread, min_dist)."""
+    spread, min_dist = float(spread), float(min_dist)
+    if not (np.isfinite(spread) and spread > 0 and np.isfinite(min_dist) and min_dist >= 0):
+        raise ValueError(f"need spread > 0 and min_dist >= 0, not {spread}, {min_dist}")
+    a, b = ctypes.c_double(0), ctypes.c_double(0)
+    call("karma_umap_ab", spread, min_dist, ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
+
+
+def umap_layout(graph, n_components, a, b, n_epochs, seed, init=None, negative_sample_rate=5, gamma=1.0,
+                initial_alpha=1.0, ctx=None):
+    """The layout of a symmetric CSR graph in gather form (karma_umap_layout;
+    include/karma.h defines every bit): graph = (indptr, indices, weights) as
+    umap_graph returns them, numpy arrays or DevBufs.  init=None starts from
+    the library's uniform [-10, 10) coordinates of `seed`; a float64 (n,
+    n_components) numpy array starts from it (and is not changed); a DevBuf of
+    that shape is updated in place and returned.  Returns float64[n,
+    n_components]."""
+    indptr, indices, weights = graph[:3]
+    device = _on_device(indptr, indices, weights)
+    if not device and any(isinstance(x, _lib.DevBuf) for x in (indptr, indices, weights)):
+        raise TypeError("the graph's three arrays must all be numpy arrays or all be DevBufs")
+    dim, n_epochs, rate, seed = int(n_components), int(n_epochs), int(negative_sample_rate), int(seed)
+    n = (indptr.size if device else len(indptr)) - 1
+    nnz = indices.size if device else len(indices)
+    if n < 2:
+        raise ValueError(f"need n >= 2, not {n}")
+    if not 1 <= dim <= 16:
+        raise ValueError(f"need 1 <= n_components <= 16, not {dim}")
+    if n_epochs < 1 or rate < 0:
+        raise ValueError(f"need n_epochs >= 1 and negative_sample_rate >= 0, not {n_epochs}, {rate}")
+    if (weights.size if device else len(weights)) != nnz:
+        raise ValueError("indices and weights must have the same length")
+    if ctx is None:
+        ctx = indptr.ctx if device else _lib.default_context()
+    pp, keep_p = _dev_or_host(indptr, np.int64)
+    pi, keep_i = _dev_or_host(indices, np.int32)
+    pw, keep_w = _dev_or_host(weights, np.float64)
+    if isinstance(init, _lib.DevBuf):
+        if init.dtype != np.float64 or init.shape != (n, dim):
+            raise ValueError(f"init must be float64 ({n}, {dim}), not {init.dtype} {init.shape}")
+        y, py, y_dev = init, ctypes.c_void_p(init.ptr), 1
+    elif init is None:
+        y = np.empty((n, dim), np.float64)
+        py, y_dev = ptr(y), 0
+    else:
+        y = np.array(init, dtype=np.float64, order="C")  # a copy: the caller's start is kept
+        if y.shape != (n, dim):
+            raise ValueError(f"init must have shape ({n}, {dim}), not {y.shape}")
+        py, y_dev = ptr(y), 0
+    call("karma_umap_layout", ctx.h, pp, pi, pw, n, nnz, 1 if device else 0, dim, float(a), float(b), n_epochs, rate,
+         float(gamma), float(initial_alpha), ctypes.c_uint64(seed & (2**64 - 1)), 1 if init is None else 0, py,
+         y_dev)
+    return y
+
+
+def umap_default_epochs(n):
+    """umap's rule: 500 epochs up to 10000 points, 200 above."""
+    return 500 if n <= 10000 else 200
+
+
+def umap(x, n_neighbors=15, n_components=2, min_dist=0.1, spread=1.0, random_state=42, n_epochs=None, init=None,
+         knn=None, ctx=None):
+    """UMAP of the rows of the float64 matrix x (n, M) on the device: exact
+    neighbour lists (knn_rows, or the (idx, dist) passed as knn=), the fuzzy
+    graph (umap_graph), the curve (umap_ab) and the layout (umap_layout) from a
+    random start (or init=).  x: what knn_rows accepts, a DeviceProfile
+    included; the lists and the graph stay on the device.  n_epochs=None: 500
+    for n <= 10000, else 200.  Returns float64[n, n_components].  Every bit is
+    defined by include/karma.h; the result is not claimed to equal
+    umap-learn's coordinates (its layout is a racy parallel SGD with its own
+    generator)."""
+    host, _, n, _, _ = _knn_source(x)
+    if ctx is None:
+        ctx = x.ctx if host is None else _lib.default_context()
+    own = []
+    try:
+        if knn is None:
+            idx, dist = knn_rows(x, n_neighbors, ctx=ctx, out_device=True)
+            own += [idx, dist]
+        else:
+            idx, dist = knn
+            if not _on_device(idx, dist):
+                idx = _lib.DevBuf.from_numpy(ctx, np.ascontiguousarray(idx, np.int32))
+                dist = _lib.DevBuf.from_numpy(ctx, np.ascontiguousarray(dist, np.float64))
+                own += [idx, dist]
+            if tuple(idx.shape) != (n, int(n_neighbors)) or tuple(dist.shape) != tuple(idx.shape):
+                raise ValueError(f"knn must be (idx, dist) of shape ({n}, {int(n_neighbors)}), not {idx.shape}")
+        graph = umap_graph(idx, dist, ctx=ctx, out_device=True)
+        own.append(graph[0])  # indices and weights are views of buffers that close with them
+        own += [g._owner for g in graph[1:]]
+        a, b = umap_ab(spread, min_dist)
+        epochs = umap_default_epochs(n) if n_epochs is None else int(n_epochs)
+        seed = 0 if random_state is None else int(random_state)
+        return umap_layout(graph, n_components, a, b, epochs, seed, init=init, ctx=ctx)
+    finally:
+        for buf in own:
+            buf.close()
+
+
 KNN_MAX_INDEX = (1 << 31) - 1  # cand_base + nc may reach it (include/karma.h, karma_knn_block)
 
 

@@ -131,7 +131,8 @@ class KmerClustering:
             fh.write("\t".join(kwargs.keys()) + "\n")
             fh.write("\t".join(str(v) for v in kwargs.values()) + "\n")
 
-    def run(self, neighbors, components, dist, r_state, min_cluster_size, device_knn=False, device_hdbscan=False):
+    def run(self, neighbors, components, dist, r_state, min_cluster_size, device_knn=False, device_hdbscan=False,
+            device_umap=False):
         """kmer.py:274-325.  The profile is computed on the GPU; UMAP/HDBSCAN
         are the reference's third-party dependencies and must be importable.
 
@@ -147,19 +148,36 @@ class KmerClustering:
         the host; include/karma.h) instead of the `hdbscan` package, which is
         then not imported and need not be installed.  Its labels are defined
         bit for bit by the library's contract and are not claimed to equal the
-        package's."""
+        package's.
+
+        device_umap (an addition; default off: nothing changes): the
+        dimension reduction is engine.umap on the profile where it lies in
+        HBM: exact neighbour lists, the fuzzy graph and the layout all on the
+        device (the lists come from there whether or not device_knn is set),
+        and `umap` is not imported.  With device_hdbscan as well, neither
+        package is imported.  Its coordinates are defined bit for bit by the
+        library's contract and are not claimed to equal umap-learn's."""
         if os.path.isfile(self.output_file):
             logger.info(f"Read from previous calculation: {self.output_file}")
             self.__read_clusters()
         else:
             logger.info("Calculate kmer profiles.")
             knn = None
-            if device_knn:
+            if device_umap:
+                kmer_profile = self.calc_kmer_profile_device()
+            elif device_knn:
                 kmer_profile, knn_idx, knn_dist = self.kmer_knn(neighbors)
                 knn = (knn_idx, knn_dist)
             else:
                 kmer_profile = self.__calc_kmer_profile()
-            if device_hdbscan:
+            if device_umap:
+                if not device_hdbscan:
+                    try:
+                        import hdbscan
+                    except ImportError as e:
+                        raise ImportError("KmerClustering.run(device_umap=True) needs hdbscan; with "
+                                          "device_hdbscan=True as well it needs neither package") from e
+            elif device_hdbscan:
                 try:
                     import umap
                 except ImportError as e:
@@ -173,13 +191,20 @@ class KmerClustering:
                     raise ImportError("KmerClustering.run needs umap-learn and hdbscan (the reference's clustering "
                                       "dependencies); the k-mer profile itself does not") from e
             logger.info("Dimension reduction with UMAP.")
-            umap_args = dict(n_neighbors=neighbors, n_components=components, min_dist=dist, random_state=r_state)
-            if knn is not None:
-                if "precomputed_knn" in inspect.signature(umap.UMAP).parameters:
-                    umap_args["precomputed_knn"] = knn
-                else:
-                    logger.warning("This umap-learn takes no precomputed_knn: UMAP searches the neighbours itself.")
-            reduced = umap.UMAP(**umap_args).fit_transform(kmer_profile)
+            if device_umap:
+                try:
+                    reduced = engine.umap(kmer_profile, neighbors, components, dist, random_state=r_state)
+                finally:
+                    kmer_profile.close()
+            else:
+                umap_args = dict(n_neighbors=neighbors, n_components=components, min_dist=dist, random_state=r_state)
+                if knn is not None:
+                    if "precomputed_knn" in inspect.signature(umap.UMAP).parameters:
+                        umap_args["precomputed_knn"] = knn
+                    else:
+                        logger.warning("This umap-learn takes no precomputed_knn: UMAP searches the neighbours "
+                                       "itself.")
+                reduced = umap.UMAP(**umap_args).fit_transform(kmer_profile)
             logger.info(f"Perform clustering with HDBSCAN. (min_cluster_size: {min_cluster_size})")
             if device_hdbscan:
                 embedding = np.ascontiguousarray(reduced, dtype=np.float64)
