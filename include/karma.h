@@ -615,6 +615,22 @@ int karma_classify_launches(uint64_t* pairs, uint64_t* flagged);
  * the job's dynamic LDS) of the classify kernel a records job of n_contigs in
  * rec_format (KARMA_REC_SORTED or KARMA_REC_FLAGGED) would launch. */
 int karma_graph_classify_occupancy(karma_ctx* ctx, int64_t n_contigs, int rec_format, int* blocks_per_cu);
+/* For tests: what the code path of a records job of n_records records over
+ * n_contigs contigs (at most 2^21, the compact path) is made of, from the
+ * function the job itself sets up with (KARMA_CHUNK, KARMA_BIN and
+ * KARMA_PART_RESIDENT in the environment are honoured as a job honours them;
+ * rec_format selects no different geometry today).  v[n], n ==
+ * KARMA_CODE_GEOMETRY_WORDS:
+ *   0 code buckets Bc            1 their width bwc (2^bwc contigs)
+ *   2 records per classify chunk 3 chunks (one code list each)
+ *   4 path: 0 no compact codes, 1 binned classify, 2 per-flush partition,
+ *     3 appended runs            5 chunk lists per partition block
+ *   6 partition blocks           7 codes per flush of the path's partition
+ *   8 reduce groups per bucket     kernel (0: none runs)
+ *   9 that kernel's resident blocks per compute unit (the occupancy query) */
+#define KARMA_CODE_GEOMETRY_WORDS 10
+int karma_graph_code_geometry(karma_ctx* ctx, int64_t n_contigs, int64_t n_records, int rec_format, int64_t* v,
+                              int n);
 /* Salmon eq classes (read_graph.py:75-114): cls_off[n_classes+1] into members
  * (contig indices as listed, duplicates kept), counts[n_classes], pair_skip[c]=1
  * when the eq_size token is "1" (read_graph.py:102).  Totals (read_graph.py:86-92)

@@ -134,6 +134,7 @@ _SIGS = {
     "karma_graph_records_end": [_c_p, _PP],
     "karma_graph_split_hint": [_c_p, _c_p, _i32],
     "karma_graph_classify_occupancy": [_c_p, _i64, _i32, ctypes.POINTER(ctypes.c_int)],
+    "karma_graph_code_geometry": [_c_p, _i64, _i64, _i32, _I64P, _i32],
     "karma_records_flag": [_c_p, _c_p, _i64, _i32, _i32, _c_p, _i32, _I64P],
     "karma_records_flag_tile": [ctypes.POINTER(ctypes.c_int)] * 3,
     "karma_classify_launches": [_c_p, _c_p],
@@ -491,6 +492,21 @@ def flag_tile():
     v = [ctypes.c_int(0) for _ in range(3)]
     call("karma_records_flag_tile", *[ctypes.byref(x) for x in v])
     return tuple(x.value for x in v)
+
+
+CODE_GEOMETRY_FIELDS = ("Bc", "bwc", "chunk", "n_chunks", "path", "lpb", "n_pblk", "flush", "n_cg", "per_cu")
+CODE_PATH_NONE, CODE_PATH_BINNED, CODE_PATH_PARTITION, CODE_PATH_APPEND = range(4)
+
+
+def code_geometry(ctx, n_contigs, n_records, flagged=False):
+    """What the code path of a records job is made of (karma_graph_code_geometry):
+    a namespace of CODE_GEOMETRY_FIELDS, from the function the job sets up with."""
+    import types
+
+    v = (ctypes.c_int64 * len(CODE_GEOMETRY_FIELDS))()
+    call("karma_graph_code_geometry", ctx.h, int(n_contigs), int(n_records),
+         KARMA_REC_FLAGGED if flagged else KARMA_REC_SORTED, v, len(v))
+    return types.SimpleNamespace(**dict(zip(CODE_GEOMETRY_FIELDS, (int(x) for x in v))))
 
 
 def knn_tile():

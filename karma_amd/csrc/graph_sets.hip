@@ -39,6 +39,7 @@
 #include <memory>
 #include <type_traits>
 
+#include "code_part.h"
 #include "karma_internal.h"
 #include "sets_ctrl.h"
 
@@ -51,15 +52,11 @@ namespace {
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxB = 2048;           // pair buckets (n_contigs <= 2^21 keeps the compact path)
-constexpr int kMaxBc = 512;           // code buckets
-// partition LDS is sized by the bucket count: the narrow variants (<= 512 pair
-// and <= 128 code buckets, n_contigs <= 2^19) keep 3 code-partition blocks per CU
-constexpr int kNarrowB = 512, kNarrowBc = 128;
-constexpr int kCrSmax = 64;  // code reduce: at most this many pieces per run
-constexpr int kCrPieces = 512;  // code reduce: split runs into pieces only while a block has < 512 (per-piece cost dominates: 2048 -> 512 took the 8-rank strong reduce 48.6 -> 26.2 us, weak 126 -> 81 us)
-constexpr int kCgShift = 18;  // a code bucket gets one reduce group per 2^18 records it may hold
+// partition LDS is sized by the bucket count: the narrow pair variant (<= 512
+// pair buckets) and the code partition (<= kNarrowBc code buckets, n_contigs
+// <= 2^19; code_part.h, with the code path's other constants)
+constexpr int kNarrowB = 512;
 constexpr int kOneGroupB = 128;
-constexpr int kAppendMinBc = 129;  // code_append_kernel from this many code buckets on (n_contigs > 2^19)
 constexpr int kMaxBwCompact = 10;     // compact reads need 2^(bw+3) band counters <= kBand
 // the compact path: kMaxB pair buckets of 2^kMaxBwCompact contigs (8 GPUs x 200k
 // contigs of a weak-scaled config 3 = 1.6M stay on it)
@@ -1184,21 +1181,18 @@ __global__ void __launch_bounds__(kGW) general_kernel(RecIn rec, int64_t A, uint
 }
 
 // ---- partition: chunk lists -> bucket-major padded runs ---------------------------
-constexpr int kPT = 512;                 // partition threads (several blocks per CU overlap their phases)
-constexpr int kMaxListsPerBlock = 128;   // chunk lists per partition block, at most (a power of 2)
-
-constexpr int kCodeFill = 8192;  // codes per partition flush (less: shorter runs for the reduce)
+// (threads, lists per block, flush sizes and part_need / append_need: code_part.h)
 // compact-read codes: u32 (m0 | M << 24) -> u16 (m0_local << 3 | M) per code bucket
 template <int NB>
 struct CodeStreamT {
     using S = uint32_t;
     using D = uint16_t;
     static constexpr int kCap = kCodeFill;  // codes per flush (8192: 32 KB of LDS)
-    static constexpr int kPad = 8;      // 16 B of u16
+    static constexpr int kPad = kCodePad;  // 16 B of u16
     static constexpr int kMaxNb = NB;
     static constexpr D kPadV = 0xFFFF;  // codes are < 2^15
-    // 3 blocks of 8 waves per CU (<= 85 VGPRs) for the narrow variant
-    static constexpr int kMinWaves = NB <= 128 ? 6 : 1;
+    // 3 blocks of 8 waves per CU (<= 85 VGPRs)
+    static constexpr int kMinWaves = 6;
     __device__ static int nb(const Geo& g) { return g.Bc; }
     __device__ static uint32_t bucket(S s, const Geo& g) { return (s & 0xFFFFFFu) >> g.bwc; }
     __device__ static D value(S s, const Geo& g) {
@@ -1224,7 +1218,6 @@ struct PairStreamT {
 };
 
 using CodeStream = CodeStreamT<kNarrowBc>;
-using CodeStreamWide = CodeStreamT<kMaxBc>;
 using PairStream = PairStreamT<kNarrowB>;
 using PairStreamWide = PairStreamT<kMaxB>;
 
@@ -1252,16 +1245,6 @@ __device__ __forceinline__ void dropped_stores() {
     const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc(nullptr, 0, 0, 0x00020000);
 #pragma unroll
     for (int t = 0; t < N; ++t) __builtin_amdgcn_raw_buffer_store_b32(0u, none, 4 * t, 0, 1 << 31);
-}
-
-// A partition block's items (blk_items, summed by the producers), flushes
-// (every flush but the last holds cap items) and an output bound (items + <
-// pad per run): the bases of block b are these sums over blocks < b, so each
-// block derives its own directory rows and stream slice (no atomics, no plan
-// launch).
-__device__ __forceinline__ void part_need(uint64_t items, int cap, int nb, int pad, int64_t* outs, int64_t* rows) {
-    *rows = ((int64_t)items + cap - 1) / cap;
-    *outs = ((int64_t)items + *rows * (int64_t)nb * (pad - 1) + pad - 1) / pad * pad;
 }
 
 template <class T>
@@ -1447,10 +1430,7 @@ partition_kernel(const typename T::S* __restrict__ lists, int64_t list_cap,
 // Here the classify kernel has already counted each partition block's codes
 // per bucket (blk_hist), so a block knows its final run for every bucket up
 // front and appends each flush's sorted segment to it: one directory row per
-// block, runs of items / Bc codes, padded once.
-__device__ __forceinline__ int64_t append_need(uint64_t items, int nb) {
-    return ((int64_t)items + (int64_t)nb * 7 + 7) / 8 * 8;
-}
+// block, runs of items / Bc codes, padded once (append_need, code_part.h).
 
 // Block barrier for LDS hand-offs only: outstanding global stores and loads are
 // not waited for (__syncthreads' release fence would drain vmcnt every flush).
@@ -1465,18 +1445,21 @@ __global__ void __launch_bounds__(kPT) code_append_kernel(const uint32_t* __rest
                                                            uint16_t* __restrict__ out, uint16_t* trash, RunDir dir,
                                                            int* err) {
     using T = CodeStreamT<NB>;
-    // codes per flush: 34 KB (narrow) / 79 KB (wide) of LDS, 4 / 2 blocks per CU;
-    // wide flushes of 8192 codes write ~20 codes per run instead of ~10
-    // (weak-scaled config 3: 0.26-0.27 vs 0.29 ms); 12288: ~30 per run, weak
-    // 8-rank preview 1.412 -> 1.397 ms; 16384 leaves one block per CU: 1.60 ms
-    constexpr int kAppendWideCap = 12288;
-    constexpr int kCap = NB > 128 ? kAppendWideCap : 4096;
+    // codes per flush (kAppendCap, code_part.h): 69 KB of LDS and 128 VGPRs, 2
+    // blocks per CU
+    constexpr int kCap = kAppendCap;
     constexpr int kPer = kCap / kPT;
     constexpr int kVMax = kCap / 8 + NB;               // 16-byte vectors of one flush, at most
     constexpr int kVPer = (kVMax + kPT - 1) / kPT;
     // a flush's codes by bucket: bucket b's pending tail (< 8 codes from earlier
-    // flushes) then its new codes, from an 8-aligned start toff[b]
-    __shared__ __attribute__((aligned(16))) uint16_t s16[kCap + 8 * NB];
+    // flushes) then its new codes, from an 8-aligned start toff[b].  The regions
+    // of one flush hold up to staged_bound codes (7 pending, 2 (mod 8) new and 7
+    // of padding in every bucket: cap + 14 NB, not cap + 8 NB).
+    constexpr int kStage = (int)staged_bound(kCap, NB);
+    static_assert(kStage >= staged_bound(kCap, NB) && kStage % 8 == 0, "s16 holds a flush's regions");
+    static_assert(kVMax >= staged_vectors(kCap, NB), "vb holds a flush's full vectors");
+    static_assert(kCap % kPT == 0 && kCap < (1 << 16), "ranks within a bucket fit 16 bits");
+    __shared__ __attribute__((aligned(16))) uint16_t s16[kStage];
     __shared__ __attribute__((aligned(16))) uint16_t pend[8 * NB];
     __shared__ uint32_t hist[2][NB + 1];
     __shared__ uint32_t toff[NB + 1];  // 8-aligned region starts in s16
@@ -1576,8 +1559,9 @@ __global__ void __launch_bounds__(kPT) code_append_kernel(const uint32_t* __rest
         if (wave == 0) {
             uint32_t c8 = 0, cq = 0;
             for (int b0 = 0; b0 < nb; b0 += 64) {
-                const uint32_t tot = b0 + lane < nb ? pc[b0 + lane] + h[b0 + lane] : 0u;
-                const uint32_t r8 = (tot + 7u) & ~7u, q = tot >> 3;
+                // (flush_bucket and its host restatement flush_scan: code_part.h)
+                const FlushBucket fb = b0 + lane < nb ? flush_bucket(pc[b0 + lane], h[b0 + lane]) : FlushBucket{};
+                const uint32_t r8 = fb.r8, q = fb.q;
                 const uint32_t sx = wave_scan_incl(r8), sy = wave_scan_incl(q);
                 if (b0 + lane < nb) {
                     toff[b0 + lane] = c8 + sx - r8;
@@ -1623,7 +1607,8 @@ __global__ void __launch_bounds__(kPT) code_append_kernel(const uint32_t* __rest
             *(t < nv ? vout + ((dlt[b] + si) >> 3) : vtrash) = val;
         }
         for (int b = threadIdx.x; b < nb; b += kPT) {
-            const uint32_t tot = pc[b] + h[b], full = tot & ~7u, r = tot & 7u;
+            const FlushBucket fb = flush_bucket(pc[b], h[b]);
+            const uint32_t full = fb.tot & ~7u, r = fb.rem;
             if (r) *reinterpret_cast<u32x4*>(pend + 8 * b) = *reinterpret_cast<const u32x4*>(s16 + toff[b] + full);
             pc[b] = r;
             wr[b] += full;
@@ -1647,8 +1632,8 @@ __global__ void __launch_bounds__(kPT) code_append_kernel(const uint32_t* __rest
 // wave takes batches of 64 runs (lane i holds run i) and reads them as one
 // stream of 16-byte vectors, 64 consecutive vectors per load; the runs a
 // window of 64 overlaps are found with wave-uniform (scalar) loops over the
-// lanes' run table, and kWin windows are in flight before they are counted.
-constexpr int kWin = 16;
+// lanes' run table, and kWin windows (code_part.h) are in flight before they
+// are counted.
 
 // slots: 64 ints of LDS per wave of the block.
 template <typename Bounds, typename Count>
@@ -1739,7 +1724,7 @@ __global__ void __launch_bounds__(kCRT) code_reduce_kernel(const uint16_t* __res
     // rows hold one long run per bucket (code_append_kernel): split each into S
     // pieces so that every wave has runs to stream
     const int64_t R = f_hi - f_lo;
-    const int S = R > 0 ? (int)max<int64_t>(1, min<int64_t>(kCrSmax, (kCrPieces + R - 1) / R)) : 1;
+    const int S = reduce_split(R);
     // LDS slot of counter c = (m0_local << 3 | M): the low five bits XOR-ed with
     // m0_local >> 2, so that codes of one wave instruction spread over all 32
     // banks (unswizzled, the bank is (m0 & 3) << 3 | M, and M is mostly 0)
@@ -2804,7 +2789,7 @@ struct SetsJob {
     int B = 0;
     int64_t n_chunks = 0;
     int64_t chunk = kCChunk;  // records per classify chunk (chunk_records)
-    bool wide_c = false, wide_p = false, append = false;
+    bool wide_p = false, append = false;
     int lpb = 0;
     int64_t n_pblk = 0;
     DevArray<uint32_t> codes, n_codes, n_gen, n_pl;
@@ -2860,24 +2845,82 @@ struct SetsJob {
     int finish(karma_pairs* out);
 };
 
-int SetsJob::setup() {
-    KARMA_TRY(make_geo(N, &g));
-    B = g.B;
-    chunk = chunk_records(ctx, A);
-    n_chunks = std::max<int64_t>(1, ceil_div(A, chunk));
-    // partition: one round of resident blocks, each taking consecutive chunk lists
-    wide_c = g.Bc > kNarrowBc;
-    wide_p = B > kNarrowB;
+struct CodeGeo {
+    Geo g;
+    int64_t chunk, n_chunks;  // records per classify chunk, chunks (and chunk lists)
+    bool append, bin;
+    int path;                 // 0 no compact codes, 1 binned classify, 2 partition_kernel<CodeStream>, 3 code_append_kernel
+    int lpb;                  // chunk lists per partition block
+    int64_t n_pblk;           // partition blocks
+    int flush;                // codes per flush of the path's partition kernel (0: none runs)
+    int64_t max_cflush;       // directory rows, at most
+    int n_cg;                 // reduce groups per code bucket
+    int per_cu;               // the code-partition kernel's resident blocks per CU
+};
+
+// the code-partition kernel's resident blocks that lpb is derived from
+// (KARMA_PART_RESIDENT in the environment lowers them, so tests reach blocks of
+// many chunk lists with few chunks; read per job)
+int part_resident(int resident) {
+    const char* e = std::getenv("KARMA_PART_RESIDENT");
+    const int v = e ? std::atoi(e) : 0;
+    return v >= 1 ? std::min(v, resident) : resident;
+}
+
+// What a records job's code path is made of: SetsJob::setup takes it from
+// here, and karma_graph_code_geometry reports it.
+int code_geometry(karma_ctx* ctx, int64_t A, int64_t N, CodeGeo* o) {
+    KARMA_TRY(make_geo(N, &o->g));
+    const Geo& g = o->g;
+    o->chunk = chunk_records(ctx, A);
+    o->n_chunks = std::max<int64_t>(1, ceil_div(A, o->chunk));
     // code partition: per-flush padded runs while a flush's runs are long (few
     // code buckets); one appended run per (block, bucket) beyond that
-    append = g.Bc >= kAppendMinBc;
-    const void* code_part = append ? (wide_c ? reinterpret_cast<const void*>(&code_append_kernel<kMaxBc>)
-                                             : reinterpret_cast<const void*>(&code_append_kernel<kNarrowBc>))
-                                   : (wide_c ? reinterpret_cast<const void*>(&partition_kernel<CodeStreamWide>)
-                                             : reinterpret_cast<const void*>(&partition_kernel<CodeStream>));
+    o->append = g.Bc >= kAppendMinBc;
+    // partition: one round of resident blocks, each taking consecutive chunk lists
+    const void* code_part = o->append ? reinterpret_cast<const void*>(&code_append_kernel<kMaxBc>)
+                                      : reinterpret_cast<const void*>(&partition_kernel<CodeStream>);
     const int resident = resident_grid(ctx, code_part, kPT, 0, int64_t(1) << 30);
-    lpb = (int)std::min<int64_t>(kMaxListsPerBlock, ceil_div(n_chunks, resident));
-    n_pblk = ceil_div(n_chunks, lpb);
+    o->per_cu = resident / std::max(1, ctx->cu_count);
+    o->lpb = (int)std::min<int64_t>(kMaxListsPerBlock, ceil_div(o->n_chunks, part_resident(resident)));
+    o->n_pblk = ceil_div(o->n_chunks, o->lpb);
+    o->bin = class_binned(g.Bc);
+    o->path = g.Bc <= 0 ? 0 : o->bin ? 1 : o->append ? 3 : 2;
+    o->flush = o->path == 3 ? kAppendCap : o->path == 2 ? CodeStream::kCap : 0;
+    // code stream: <= one code per record + < 8 padding codes per run; a block
+    // flushes only a full buffer, and once at its end
+    o->max_cflush = o->n_pblk + ceil_div(A, CodeStream::kCap) + 1;
+    // reduce geometry: grids fixed here, flush ranges from device counters
+    // code reduce: one round (one 128 KB-LDS block per CU), at most ~4 flushes per group
+    // Groups also cost a 128 KB histogram clear and write-back each (and the
+    // final kernel sums them), so a bucket gets one group per ~256K records it
+    // may hold (8-way strong scaling of config 3: 3 groups; one group took
+    // 0.076 ms against 0.047 for five).
+    o->n_cg = g.Bc > 0 ? (int)std::max<int64_t>(1, std::min<int64_t>({ctx->cu_count / g.Bc, ceil_div(o->max_cflush, 4),
+                                                                        ceil_div(A, (int64_t)g.Bc << kCgShift)}))
+                       : 0;
+    // binned: one group per ~64 chunks at most (a wave's batch), up to one block
+    // per CU, and one per 2^19 records a bucket may hold (each group clears and
+    // writes back a 128 KB histogram the final kernel sums: at the 8-rank
+    // strong preview's 38.6M records 2 groups per bucket instead of 5 took
+    // 0.183-0.184 against 0.190-0.192 ms per step; 1: 0.185, 3: 0.188)
+    if (o->bin)
+        o->n_cg = (int)std::max<int64_t>(1, std::min<int64_t>({ctx->cu_count / g.Bc, ceil_div(o->n_chunks, 64),
+                                                               ceil_div(A, (int64_t)g.Bc << 19)}));
+    return KARMA_OK;
+}
+
+int SetsJob::setup() {
+    CodeGeo cg{};
+    KARMA_TRY(code_geometry(ctx, A, N, &cg));
+    g = cg.g;
+    B = g.B;
+    chunk = cg.chunk;
+    n_chunks = cg.n_chunks;
+    wide_p = B > kNarrowB;
+    append = cg.append;
+    lpb = cg.lpb;
+    n_pblk = cg.n_pblk;
     KARMA_TRY(codes.alloc(ctx, n_chunks * chunk));
     KARMA_TRY(n_codes.alloc(ctx, n_chunks));
     KARMA_TRY(n_gen.alloc(ctx, n_chunks));
@@ -2913,12 +2956,10 @@ int SetsJob::setup() {
         KARMA_TRY(ctx_job_pinned(ctx, cl.readback * 8, &hpin));
         hctrl = static_cast<const int64_t*>(hpin);
     }
-    // code stream: <= one code per record + < 8 padding codes per run; a block
-    // flushes only a full buffer, and once at its end
-    max_cflush = n_pblk + ceil_div(A, CodeStream::kCap) + 1;
+    max_cflush = cg.max_cflush;
     ccap = A + max_cflush * (8 * (int64_t)g.Bc + 8);
     if (append) KARMA_TRY(blk_hist.alloc(ctx, n_pblk * g.Bc));
-    bin = class_binned(g.Bc);
+    bin = cg.bin;
     if (bin) {
         dir_cap = (int)(chunk / kBinQ);
         seg_cap = (uint32_t)(dir_cap + g.Bc);
@@ -2937,23 +2978,7 @@ int SetsJob::setup() {
         KARMA_TRY(cf_base.alloc(ctx, max_cflush));
         KARMA_TRY(cf_off.alloc(ctx, max_cflush * (g.Bc + 1)));
     }
-    // reduce geometry: grids fixed here, flush ranges from device counters
-    // code reduce: one round (one 128 KB-LDS block per CU), at most ~4 flushes per group
-    // Groups also cost a 128 KB histogram clear and write-back each (and the
-    // final kernel sums them), so a bucket gets one group per ~256K records it
-    // may hold (8-way strong scaling of config 3: 3 groups; one group took
-    // 0.076 ms against 0.047 for five).
-    n_cg = g.Bc > 0 ? (int)std::max<int64_t>(1, std::min<int64_t>({ctx->cu_count / g.Bc, ceil_div(max_cflush, 4),
-                                                                     ceil_div(A, (int64_t)g.Bc << kCgShift)}))
-                    : 0;
-    // binned: one group per ~64 chunks at most (a wave's batch), up to one block
-    // per CU, and one per 2^19 records a bucket may hold (each group clears and
-    // writes back a 128 KB histogram the final kernel sums: at the 8-rank
-    // strong preview's 38.6M records 2 groups per bucket instead of 5 took
-    // 0.183-0.184 against 0.190-0.192 ms per step; 1: 0.185, 3: 0.188)
-    if (bin)
-        n_cg = (int)std::max<int64_t>(1, std::min<int64_t>({ctx->cu_count / g.Bc, ceil_div(n_chunks, 64),
-                                                            ceil_div(A, (int64_t)g.Bc << 19)}));
+    n_cg = cg.n_cg;  // the code reduce's groups per bucket (code_geometry)
     // pair-reduce groups per bucket: enough blocks to fill the chip while
     // buckets are few; one group from kOneGroupB buckets on, so the
     // final kernel copies the bucket's single list instead of re-hashing
@@ -3089,15 +3114,9 @@ int SetsJob::launch() {
         KARMA_TRY(mark(2));
     } else if (g.Bc > 0) {
         uint16_t* const trash = cent.ptr + (ccap + 7) / 8 * 8;
-        if (append && wide_c)
+        if (append)
             KARMA_LAUNCH(ctx, "graph_code_partition", code_append_kernel<kMaxBc>, n_pblk, kPT, 0, codes.ptr, chunk,
                          n_codes.ptr, n_chunks, lpb, g, blk_hist.ptr, cent.ptr, trash, cdir, flags + kFlagPartition);
-        else if (append)
-            KARMA_LAUNCH(ctx, "graph_code_partition", code_append_kernel<kNarrowBc>, n_pblk, kPT, 0, codes.ptr, chunk,
-                         n_codes.ptr, n_chunks, lpb, g, blk_hist.ptr, cent.ptr, trash, cdir, flags + kFlagPartition);
-        else if (wide_c)
-            KARMA_LAUNCH(ctx, "graph_code_partition", partition_kernel<CodeStreamWide>, n_pblk, kPT, 0, codes.ptr,
-                         chunk, n_codes.ptr, n_chunks, lpb, g, cent.ptr, cdir);
         else
             KARMA_LAUNCH(ctx, "graph_code_partition", partition_kernel<CodeStream>, n_pblk, kPT, 0, codes.ptr, chunk,
                          n_codes.ptr, n_chunks, lpb, g, cent.ptr, cdir);
@@ -3368,6 +3387,22 @@ int records_to_pairs_sets(karma_ctx* ctx, RecIn rec, int64_t A, int64_t N, karma
 }
 
 }  // namespace karma
+
+extern "C" int karma_graph_code_geometry(karma_ctx* ctx, int64_t n_contigs, int64_t n_records, int rec_format,
+                                         int64_t* v, int n) {
+    using namespace karma;
+    KARMA_CHECK(ctx && v && n == KARMA_CODE_GEOMETRY_WORDS && n_contigs >= 1 && n_contigs <= kMaxCompactN &&
+                    n_records >= 0 && (rec_format == KARMA_REC_SORTED || rec_format == KARMA_REC_FLAGGED),
+                KARMA_ERR_ARG, "karma_graph_code_geometry: bad arguments (n_contigs %lld, n_records %lld, n %d)",
+                (long long)n_contigs, (long long)n_records, n);
+    KARMA_TRY(ctx_begin(ctx));
+    CodeGeo cg{};
+    KARMA_TRY(code_geometry(ctx, n_records, n_contigs, &cg));
+    const int64_t out[KARMA_CODE_GEOMETRY_WORDS] = {cg.g.Bc, cg.g.bwc, cg.chunk, cg.n_chunks, cg.path,
+                                                    cg.lpb,  cg.n_pblk, cg.flush, cg.n_cg,    cg.per_cu};
+    std::copy(out, out + n, v);
+    return KARMA_OK;
+}
 
 extern "C" int karma_graph_classify_occupancy(karma_ctx* ctx, int64_t n_contigs, int rec_format,
                                               int* blocks_per_cu) {
