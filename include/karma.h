@@ -939,6 +939,91 @@ int karma_adj_destroy(karma_adj* g);
 /* Host build of the device's repr(float) formatter, for tests: one line per value. */
 int karma_repr_f64_host(const double* x, int64_t n, char* out, int64_t cap, int64_t* len);
 
+/* ---- MCL: Markov clustering of a weighted graph -------------------------------
+ * karma.py:317-318 and :372-373 pipe ReadGraph.edge_list() into the external
+ * `mcl` binary (karma/mcl.py:48-51: -I <inflation> --abc -resource 4).  The
+ * process below is defined here, bit for bit; equality with the binary's
+ * clusters is not claimed (its pruning -- cutoff, selection, recovery, pct --
+ * is richer than "keep the R largest" and has a tie order of its own).  What
+ * is kept is what -resource 4 is for, at most R entries per column, and MCL's
+ * usual defaults: loops of the column's maximum, inflation 2, cutoff 1/4000.
+ *
+ * Input: a graph as CSR in karma_adj_get's layout, off int64[n + 1], nbr
+ * uint32[nnz], w f64[nnz] (nnz = off[n]), on the host or the device; rows need
+ * not be sorted.  Column j of the matrix is CSR row j (no difference for the
+ * symmetric graphs of a karma_adj).  1 <= n < 2^31, nnz < 2^31, 2 <= resource
+ * (R) <= 32, 1.0 < inflation <= 16.0, 2^-40 <= cutoff <= 0.5, 0 <= eps,
+ * max_iter >= 1, weights finite and > 0.
+ *
+ * Start.  Column j's entries are those with i = nbr[e] != j, value w[e];
+ * entries naming j itself are ignored; the same i twice in one column is
+ * KARMA_ERR_ARG.  The loop (j, m) is added, m the column's largest value, or
+ * 1.0 for an empty column.  Entries ordered by row ascending; s = their
+ * in-order sum from +0.0; T[i, j] = v / s.
+ *
+ * Iteration t = 1, 2, ...: every column j independently, on the previous T;
+ * every step one IEEE f64 operation, no contraction.
+ *   expand   for k over column j's rows ascending and i over column k's rows,
+ *            the candidate p = T[i, k] * T[k, j]; X[i] = the sum of its
+ *            candidates in ascending k from +0.0.
+ *   prune    rows ordered by (X descending, i ascending); the first is kept;
+ *            of the next R - 1 those with X[i] >= cutoff; s = the kept values'
+ *            sum in ascending row order from +0.0; x = X / s.
+ *   inflate  y = x * x when inflation == 2.0, else kpow(x, inflation) (the
+ *            library's own, csrc/umap_math.h); s2 = the row-ascending sum of
+ *            the y from +0.0; z = y / s2 is the new T[i, j].  Within the limits
+ *            above every z > 0: x >= 2^-40 / 33 and inflation <= 16 keep y far
+ *            above the smallest normal number.
+ *   chaos    chaos_j = max_i z - (the row-ascending sum of z * z from +0.0);
+ *            chaos = max_j chaos_j (an f64 maximum; a chaos_j may be a rounding
+ *            error below zero, and is compared as it is).
+ *   stop     after the first iteration with chaos < eps, or at t == max_iter.
+ * A uniform clique converges in one iteration with all its members attractors
+ * of one system (its R smallest members when it has more than R).  The result does not depend on block shape, path (general or
+ * fused), batch size (cand_cap) or launch order.
+ *
+ * karma_mcl returns the final matrix as CSC: colptr int64[n + 1], rows
+ * uint32 and vals f64 (each column ascending by row, at least one entry), in
+ * buffers of cap >= n * resource entries (less: KARMA_ERR_ARG), on the host or
+ * the device; *iterations and *chaos (host words) are those of the last
+ * iteration run.  flags & KARMA_MCL_GENERAL: every iteration takes the general
+ * path (sort-based, any column width; always used for iteration 1 and for
+ * R > 8); otherwise iterations >= 2 run in one fused launch each.  cand_cap:
+ * most candidates of one batch of the general path (whole columns; never less
+ * than the widest column's count; 0: the default).  Argument errors
+ * (KARMA_ERR_ARG, with a message) are found before a device is looked for; a
+ * host graph's contents too; a device graph's contents by the first kernels,
+ * before anything is indexed with them.  Timing-table names: mcl_start,
+ * mcl_expand (general path), mcl_iter (fused path). */
+#define KARMA_MCL_GENERAL 1
+int karma_mcl(karma_ctx* ctx, int64_t n, const int64_t* off, const uint32_t* nbr, const double* w, int in_is_device,
+              double inflation, int resource, double cutoff, double eps, int max_iter, int flags, int64_t cand_cap,
+              int64_t* colptr, uint32_t* rows, double* vals, int64_t cap, int32_t* iterations, double* chaos,
+              int out_is_device);
+/* The same on a karma_adj's own device arrays: nothing is copied to the host. */
+int karma_adj_mcl(karma_adj* g, double inflation, int resource, double cutoff, double eps, int max_iter, int flags,
+                  int64_t cand_cap, int64_t* colptr, uint32_t* rows, double* vals, int64_t cap, int32_t* iterations,
+                  double* chaos, int out_is_device);
+/* The clusters of a final matrix (CSC, columns non-empty and ascending by
+ * row), on the host: no device, no context.
+ *   attractors  A = {a : T[a, a] present}.
+ *   systems     the connected components of A under a ~ b when T[a, b] or
+ *               T[b, a] is present.
+ *   assignment  node j (attractors included) joins the system with the largest
+ *               mass, a system's mass being the row-ascending sum from +0.0 of
+ *               column j's entries on that system's attractors; ties go to the
+ *               system whose smallest attractor is smallest.  A column with no
+ *               entry on an attractor makes j a cluster of its own (possible
+ *               only when max_iter stopped the run).
+ *   labels      int32[n]: the rank of j's cluster under (size descending,
+ *               smallest member ascending); *n_clusters their number. */
+int karma_mcl_clusters(int64_t n, const int64_t* colptr, const uint32_t* rows, const double* vals, int32_t* labels,
+                       int32_t* n_clusters);
+/* For tests that place cases on the edges.  Fills the first n of v[0..3]:
+ * columns per block of the fused kernel (resource <= 4), lanes per column for
+ * resource <= 4 and for resource <= 8, the default cand_cap. */
+int karma_mcl_tile(int* v, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,7 @@ KARMA_STEP_FLAGGED = 8
 KARMA_MODE_READS = 0
 KARMA_MODE_EQ = 1
 KARMA_STEP_KEEP, KARMA_STEP_SEQUENTIAL, KARMA_STEP_DEFER = 1, 2, 4
+KARMA_MCL_GENERAL = 1
 
 _c_p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -209,6 +210,13 @@ _SIGS = {
     "karma_adj_cross_sums": [_c_p, _c_p, _c_p, ctypes.c_double, _c_p, _c_p, _c_p, _c_p, _i64, _I64P],
     "karma_adj_destroy": [_c_p],
     "karma_repr_f64_host": [_c_p, _i64, _c_p, _i64, _I64P],
+    "karma_mcl": [_c_p, _i64, _c_p, _c_p, _c_p, _i32, ctypes.c_double, _i32, ctypes.c_double, ctypes.c_double, _i32,
+                  _i32, _i64, _c_p, _c_p, _c_p, _i64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
+                  _i32],
+    "karma_adj_mcl": [_c_p, ctypes.c_double, _i32, ctypes.c_double, ctypes.c_double, _i32, _i32, _i64, _c_p, _c_p,
+                      _c_p, _i64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), _i32],
+    "karma_mcl_clusters": [_i64, _c_p, _c_p, _c_p, _c_p, ctypes.POINTER(ctypes.c_int32)],
+    "karma_mcl_tile": [_c_p, _i32],
 }
 
 EXPORTED = tuple(_SIGS) + ("karma_last_error", "karma_comm_id_bytes", "karma_build_info")
@@ -528,6 +536,14 @@ def umap_tile():
     v = ctypes.c_int(0)
     call("karma_umap_tile", ctypes.byref(v))
     return v.value
+
+
+def mcl_tile():
+    """The MCL kernels' constants (karma_mcl_tile): columns per block of the fused kernel, lanes per column
+    for resource <= 4 and for resource <= 8, the default cand_cap."""
+    v = np.zeros(4, np.int32)
+    call("karma_mcl_tile", ptr(v), 4)
+    return types.SimpleNamespace(COLS=int(v[0]), LANES4=int(v[1]), LANES8=int(v[2]), CAND_CAP=int(v[3]))
 
 
 def knn_block_split(ctx, nq, nc, cand_split=0):

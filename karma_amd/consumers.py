@@ -189,6 +189,23 @@ class DeviceAdj:
                  ptr(no), p, ctypes.byref(P))
         return (pair >> np.uint64(32)).astype(np.int64), (pair & np.uint64(0xFFFFFFFF)).astype(np.int64), s, ne, no
 
+    def mcl(self, inflation=2.0, resource=4, cutoff=1 / 4000, eps=1e-3, max_iter=100, general=False, cand_cap=0,
+            out_device=False):
+        """Markov clustering of this graph on its own device arrays
+        (karma_adj_mcl): engine.mcl's result, (colptr, rows, vals, iterations,
+        chaos), with nothing of the graph copied to the host."""
+        from . import engine
+
+        if self.n < 1:
+            raise ValueError("need n >= 1")
+        opts = engine._mcl_options(inflation, resource, cutoff, eps, max_iter, general, cand_cap)
+        cap, colptr, rows, vals, arg = engine._mcl_outputs(self.ctx, self.n, opts[1], out_device)
+        it, chaos = ctypes.c_int32(0), ctypes.c_double(0.0)
+        call("karma_adj_mcl", self.h, opts[0], opts[1], opts[2], opts[3], opts[4], opts[5], opts[6], arg(colptr),
+             arg(rows), arg(vals), cap, ctypes.byref(it), ctypes.byref(chaos), 1 if out_device else 0)
+        rows, vals = engine._mcl_result(self.ctx, self.n, colptr, rows, vals, out_device)
+        return colptr, rows, vals, it.value, chaos.value
+
     def edge_list(self, names: NameTable) -> bytes:
         dn, do = names.device()
         n = _lib._i64(0)

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "karma_internal.h"
+#include "mcl_args.h"
 #include "repr.h"
 
 using namespace karma;
@@ -865,6 +866,20 @@ int karma_adj_get(karma_adj* g, uint32_t* ids, int64_t* off, uint32_t* nbr, doub
     if (w && g->m) KARMA_HIP(hipMemcpyAsync(w, g->w.ptr, g->m * 8, hipMemcpyDeviceToHost, ctx->stream));
     KARMA_HIP(hipStreamSynchronize(ctx->stream));
     return KARMA_OK;
+}
+
+int karma_adj_mcl(karma_adj* g, double inflation, int resource, double cutoff, double eps, int max_iter, int flags,
+                  int64_t cand_cap, int64_t* colptr, uint32_t* rows, double* vals, int64_t cap, int32_t* iterations,
+                  double* chaos, int out_is_device) {
+    KARMA_CHECK(g, KARMA_ERR_ARG, "null graph");
+    MclArgError bad = mcl_check_options(inflation, resource, cutoff, eps, max_iter, flags, cand_cap);
+    if (bad == kMclArgsOk) bad = mcl_check_outputs(g->n, resource, colptr, rows, vals, cap, iterations, chaos);
+    KARMA_CHECK(bad == kMclArgsOk, KARMA_ERR_ARG, "%s", mcl_arg_message(bad));
+    KARMA_TRY(karma_adj_info(g, nullptr, &g->m));
+    KARMA_CHECK(g->m < kMclMaxN, KARMA_ERR_ARG, "%s", mcl_arg_message(kMclArgsOff));
+    KARMA_TRY(ctx_begin(g->ctx));
+    return mcl_run(g->ctx, g->n, g->m, g->off.ptr, g->nbr.ptr, g->w.ptr, inflation, resource, cutoff, eps, max_iter,
+                   flags, cand_cap, colptr, rows, vals, iterations, chaos, out_is_device);
 }
 
 int karma_adj_degrees(karma_adj* g, int64_t* deg) {

@@ -232,6 +232,12 @@ int radix_sort_u32(karma_ctx* ctx, const uint32_t* kin, const uint32_t* vin, int
 int reduce_sorted(karma_ctx* ctx, const uint64_t* keys, const uint32_t* perm, const int64_t* cin,
                   const uint64_t* fin, int64_t n, uint64_t* uk, int64_t* uc, uint64_t* uf, int64_t* n_out_dev);
 
+// mcl.hip: Markov clustering of a device CSR graph (off n + 1, nbr / w nnz), the
+// arguments already checked (mcl_args.h); what karma_mcl and karma_adj_mcl share
+int mcl_run(karma_ctx* ctx, int64_t n, int64_t nnz, const int64_t* off_d, const uint32_t* nbr_d, const double* w_d,
+            double inflation, int resource, double cutoff, double eps, int max_iter, int flags, int64_t cand_cap,
+            int64_t* colptr, uint32_t* rows, double* vals, int32_t* iterations, double* chaos, int out_is_device);
+
 // k-mer plan internals for karma_step (kmer.hip)
 // A zeroed block of the caller's that a plan may take for its presence bitmap
 // and exception counter (no clearing memset); the plan's column table kernel

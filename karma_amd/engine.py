@@ -527,6 +527,99 @@ def umap_graph(idx, dist, ctx=None, out_device=False, with_sigma=False):
     return (indptr, indices, weights, sigma, rho) if with_sigma else (indptr, indices, weights)
 
 
+def _mcl_options(inflation, resource, cutoff, eps, max_iter, general, cand_cap):
+    inflation, resource, cutoff, eps = float(inflation), int(resource), float(cutoff), float(eps)
+    max_iter, cand_cap = int(max_iter), int(cand_cap)
+    if not 2 <= resource <= 32:
+        raise ValueError(f"need 2 <= resource <= 32, not {resource}")
+    if not 1.0 < inflation <= 16.0:
+        raise ValueError(f"need 1 < inflation <= 16, not {inflation}")
+    if not 2.0 ** -40 <= cutoff <= 0.5:
+        raise ValueError(f"need 2^-40 <= cutoff <= 0.5, not {cutoff}")
+    if not eps >= 0.0:
+        raise ValueError(f"need eps >= 0, not {eps}")
+    if max_iter < 1:
+        raise ValueError(f"need max_iter >= 1, not {max_iter}")
+    if not 0 <= cand_cap < 2 ** 32:
+        raise ValueError(f"need 0 <= cand_cap < 2^32, not {cand_cap}")
+    return inflation, resource, cutoff, eps, max_iter, _lib.KARMA_MCL_GENERAL if general else 0, cand_cap
+
+
+def _mcl_outputs(ctx, n, resource, out_device):
+    cap = n * resource
+
+    def make(count, dtype):
+        return _lib.DevBuf(ctx, (count,), dtype) if out_device else np.empty(count, dtype)
+
+    def arg(buf):
+        return ctypes.c_void_p(buf.ptr) if out_device else ptr(buf)
+
+    return cap, make(n + 1, np.int64), make(cap, np.uint32), make(cap, np.float64), arg
+
+
+def _mcl_result(ctx, n, colptr, rows, vals, out_device):
+    """Trim rows and vals to the matrix's entries (a device result's count is read back)."""
+    if out_device:
+        last = np.zeros(1, np.int64)
+        call("karma_memcpy", ctx.h, ptr(last), ctypes.c_void_p(colptr.ptr + 8 * n), 8, 1)
+        return rows.view(0, int(last[0])), vals.view(0, int(last[0]))
+    return rows[:colptr[n]].copy(), vals[:colptr[n]].copy()
+
+
+def mcl(off, nbr, w, inflation=2.0, resource=4, cutoff=1 / 4000, eps=1e-3, max_iter=100, general=False, cand_cap=0,
+        ctx=None, out_device=False):
+    """Markov clustering of a weighted graph on the device (karma_mcl; the
+    contract is in include/karma.h): the graph as CSR in karma_adj_get's layout,
+    off int64[n + 1], nbr uint32[nnz], w float64[nnz], all numpy arrays or all
+    DevBufs.  Returns (colptr int64[n + 1], rows uint32, vals float64,
+    iterations, chaos): the final matrix as CSC, numpy arrays, or DevBufs with
+    out_device=True.  general=True keeps every iteration on the sort-based
+    general path; cand_cap bounds a batch of it (0: the default).  Every bit is
+    defined by the contract; equality with the `mcl` binary's clusters is not
+    claimed (its pruning is richer and has a tie order of its own)."""
+    device = _on_device(off, nbr, w)
+    if not device and any(isinstance(a, _lib.DevBuf) for a in (off, nbr, w)):
+        raise TypeError("off, nbr and w must all be numpy arrays or all be DevBufs")
+    n = int((off.shape if device else np.shape(off))[0]) - 1
+    if n < 1:
+        raise ValueError("need n >= 1")
+    opts = _mcl_options(inflation, resource, cutoff, eps, max_iter, general, cand_cap)
+    if ctx is None:
+        ctx = off.ctx if device else _lib.default_context()
+    po, keep_o = _dev_or_host(off, np.int64)
+    pn, keep_n = _dev_or_host(nbr, np.uint32)
+    pw, keep_w = _dev_or_host(w, np.float64)
+    if not device and not len(keep_n) == len(keep_w) >= int(keep_o[-1]):
+        raise ValueError("nbr and w must each hold off[n] entries")
+    cap, colptr, rows, vals, arg = _mcl_outputs(ctx, n, opts[1], out_device)
+    it, chaos = ctypes.c_int32(0), ctypes.c_double(0.0)
+    call("karma_mcl", ctx.h, n, po, pn, pw, 1 if device else 0, opts[0], opts[1], opts[2], opts[3], opts[4], opts[5],
+         opts[6], arg(colptr), arg(rows), arg(vals), cap, ctypes.byref(it), ctypes.byref(chaos),
+         1 if out_device else 0)
+    rows, vals = _mcl_result(ctx, n, colptr, rows, vals, out_device)
+    return colptr, rows, vals, it.value, chaos.value
+
+
+def mcl_clusters(colptr, rows, vals):
+    """The clusters of a final MCL matrix, on the host (karma_mcl_clusters; no
+    device needed): attractors, their systems, every node with the system that
+    holds the largest mass of its column.  Returns (labels int32[n],
+    n_clusters); labels rank the clusters by (size descending, smallest member
+    ascending)."""
+    colptr = np.ascontiguousarray(colptr, np.int64)
+    rows = np.ascontiguousarray(rows, np.uint32)
+    vals = np.ascontiguousarray(vals, np.float64)
+    n = len(colptr) - 1
+    if n < 1:
+        raise ValueError("need n >= 1")
+    if not len(rows) == len(vals) >= int(colptr[-1]):
+        raise ValueError("rows and vals must each hold colptr[n] entries")
+    labels = np.empty(n, np.int32)
+    count = ctypes.c_int32(0)
+    call("karma_mcl_clusters", n, ptr(colptr), ptr(rows), ptr(vals), ptr(labels), ctypes.byref(count))
+    return labels, count.value
+
+
 def umap_ab(spread=1.0, min_dist=0.1):
     """umap's find_ab_params (karma_umap_ab, on the host: no device needed):
     (a, b) of the curve 1 / (1 + a x^(2b)) fitted to the membership curve of

@@ -476,6 +476,37 @@ class ReadGraph(nx.Graph):
         m = self._device_mirror()
         return m.adj.edge_list(m.names)
 
+    def mcl(self, inflation: float = 2.0, resource: int = 4) -> str:
+        """Markov clustering of this graph on the device, with no text in
+        between: the stdout the `mcl` binary would answer edge_list() with
+        (karma.py:317-318), as karma_amd.mcl.Mcl.run_pipe(self.edge_list())
+        gives it.  One line per cluster in label order, members tab-separated,
+        each line ending with a newline; nodes without an edge are left out (the
+        binary never sees them).  Nodes are numbered as the binary meets them,
+        by first appearance in edge_list(), which is also the members' order in
+        a line.  The host reads the layout only to find that order; the process
+        runs on the mirror's own device arrays (DeviceAdj.mcl on a view of the
+        mirror in that order)."""
+        from .mcl import cluster_text
+
+        m = self._device_mirror()
+        _, off, nbr, _ = m.adj.layout()
+        # G.edges(): per node u in order, its neighbours not yet iterated as u (v >= u in positions)
+        u = np.repeat(np.arange(m.adj.n, dtype=np.int64), np.diff(off))
+        first = nbr.astype(np.int64) >= u
+        seq = np.stack([u[first], nbr[first].astype(np.int64)], axis=1).ravel()
+        if not len(seq):
+            return ""
+        present, where = np.unique(seq, return_index=True)
+        order = present[np.argsort(where, kind="stable")]
+        view = m.adj.view(order)
+        try:
+            colptr, rows, vals, _, _ = view.mcl(inflation=float(inflation), resource=int(resource))
+        finally:
+            view.close()
+        labels, count = engine.mcl_clusters(colptr, rows, vals)
+        return cluster_text(labels, count, [m.nodes[p] for p in order.tolist()])
+
     def calc_distance_between_subgraphs(self, nodes_a: list, nodes_b: list) -> int:
         """Sum of weights between two node sets (read_graph.py:359-373)."""
         total = 0
