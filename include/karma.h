@@ -549,6 +549,94 @@ int karma_umap_layout(karma_ctx* ctx, const int64_t* indptr, const int32_t* indi
  * and >= 0. */
 int karma_umap_ab(double spread, double min_dist, double* a, double* b);
 
+/* ---- UMAP: spectral start, component by component ------------------------------ */
+/* karma_graph_components: the connected components of a CSR graph read as
+ * undirected (an entry (i, j) joins i and j; weights are not looked at).
+ * comp[i] (int32[n], host or device: comp_is_device) is the smallest vertex of
+ * i's component; *n_comp (host) their number.  Labels hook to the minimum and
+ * jump to the root in rounds, the host reading one "changed" word per round; at
+ * most 2 ceil(log2 n) + 1 rounds (spectral_args.h argues the bound), beyond
+ * which KARMA_ERR_STATE.  Integer atomics only: the result is a set property.
+ * 1 <= n < 2^31.  KARMA_ERR_ARG as karma_umap_layout's (a host graph before a
+ * device is looked for, a device graph by the first kernel).  Kernel name in the
+ * timing table: graph_components. */
+int karma_graph_components(karma_ctx* ctx, const int64_t* indptr, const int32_t* indices, int64_t n, int64_t nnz,
+                           int graph_is_device, int32_t* comp, int comp_is_device, int64_t* n_comp);
+/* karma_spectral_apply: out = S x for a block x (f64 n x p row-major, 1 <= p <=
+ * 32; x and out both host or both device: x_is_device), S = D^-1/2 W D^-1/2 of
+ * the CSR graph, every bit defined:
+ *   d(i)    the in-order sum from +0.0 of row i's weights; isd(i) = 1.0 /
+ *           sqrt(d(i))
+ *   (S x)[i, c] = isd(i) * (the sum over row i's entries (column j, weight w)
+ *           in CSR order, from +0.0, of (w * isd(j)) * x[j, c]); +0.0 for an
+ *           empty row, which is a component of its own
+ * each step one IEEE f64 operation, no contraction.  A row's loads do not depend
+ * on its running sum: only the additions chain. */
+int karma_spectral_apply(karma_ctx* ctx, const int64_t* indptr, const int32_t* indices, const double* weights,
+                         int64_t n, int64_t nnz, int graph_is_device, const double* x, int p, double* out,
+                         int x_is_device);
+/* Rows per tile of the solver's reordered block, the block's guard columns
+ * (p = dim + guard) and the Chebyshev filter's degree, for tests and tools. */
+int karma_spectral_tile(int* rows_per_tile, int* guard, int* degree);
+/* Wall milliseconds of this thread's last karma_umap_spectral, for tools: ms[0]
+ * labelling the components, ms[1] the reorder, ms[2] the outer rounds, ms[3]
+ * (inside ms[2]) the host's small dense problems. */
+int karma_spectral_last_ms(double* ms);
+/* The solver's small symmetric eigenproblem on the host (no device, no
+ * context): cyclic Jacobi on the p x p matrix (a + a^T) / 2, 1 <= p <= 33;
+ * w[p] the eigenvalues descending, column k of v (v[i * p + k]) the k-th
+ * eigenvector.  KARMA_ERR_STATE if 64 sweeps do not settle it. */
+int karma_spectral_jacobi(const double* a, int p, double* w, double* v);
+/* karma_umap_spectral: start coordinates y (f64 n x dim) for karma_umap_layout
+ * (init == 0) from the bottom eigenvectors of the normalised Laplacian of a
+ * symmetric CSR graph (karma_umap_graph's), solved per connected component.
+ * This is umap's per-component spectral layout (multi_component_layout) with
+ * its meta-placement of the components restated without the data matrix;
+ * equality with umap-learn's coordinates is not claimed.  Optional outputs
+ * (null: not written): vec, lam, res (f64 n x dim each), comp (int32[n]); all
+ * outputs host or device (out_is_device); info (int64[4], host): components,
+ * components not converged, outer rounds run, operator applications.
+ *
+ * Exact, bit for bit:
+ *   operator    karma_spectral_apply's S; components karma_graph_components'.
+ *   per component C (s vertices, smallest vertex r, m = min(dim, s - 1)):
+ *     vec[i, c] (i in C, c < m) is the unit eigenvector of S restricted to C for
+ *     its c-th largest eigenvalue theta_c on the complement of sqrt(d), its
+ *     sign fixed so that the entry of largest magnitude, first by vertex, is
+ *     positive; columns c >= m are +0.0.  lam[r, c] = 1 - theta_c, res[r, c] =
+ *     |S v - theta_c v|_2 as the solver measured it; rows of other vertices
+ *     hold +0.0.  C is converged iff its m residuals are all <= tol (a single
+ *     vertex always is).
+ *   composition unit(sd, i, c) = (splitmix64(sd + (i * dim + c + 1) *
+ *     0x9E3779B97F4A7C15) >> 11) * 2^-53 (karma_umap_layout's start, u64
+ *     arithmetic);
+ *       centre_C[c] = (-10.0 + 20.0 * unit(seed, r, c)) * (1.0 - (double)s /
+ *                     (double)n)         (one connected graph is centred at 0)
+ *       R_C    = 10.0 * kpow((double)s / (double)n, 1.0 / (double)dim)
+ *       vmax_C = the largest |vec[i, c]| over i in C, c < m
+ *       y[i, c] = (centre_C[c] + (R_C / vmax_C) * vec[i, c]) + 1e-4 * (-1.0 +
+ *                 2.0 * unit(seed + 1, i, c)); for m == 0 or c >= m:
+ *                 centre_C[c] + 1e-4 * (...).  The last term plays the part of
+ *                 umap's noise: coincident points would never part (d2 == 0
+ *                 makes no move).
+ *     A component that did not converge takes karma_umap_layout's random start
+ *     on its rows: y[i, c] = -10.0 + 20.0 * unit(seed, i, c).
+ * Judged by properties, not bits (as karma_umap_ab's fit): the eigenvectors
+ * themselves.  The solver is a Chebyshev-filtered subspace iteration with
+ * Rayleigh-Ritz on a block of dim + 6 columns, at most max_outer rounds per
+ * component; it is deterministic -- no float atomics, every reduction in an
+ * order fixed by the graph's shape -- so two calls, and a host and a device
+ * graph, give the same bytes.  A component that does not converge is reported
+ * in res and info, not as an error.
+ * limits: 1 <= dim <= 16; 2 <= n < 2^31; tol finite and > 0; max_outer >= 1;
+ * weights finite and > 0; the graph symmetric (not checked: an asymmetric one
+ * does not converge).  KARMA_ERR_ARG as karma_umap_layout's.  Kernel name in the
+ * timing table: umap_spectral. */
+int karma_umap_spectral(karma_ctx* ctx, const int64_t* indptr, const int32_t* indices, const double* weights,
+                        int64_t n, int64_t nnz, int graph_is_device, int dim, uint64_t seed, double tol, int max_outer,
+                        double* y, double* vec, double* lam, double* res, int32_t* comp, int out_is_device,
+                        int64_t* info);
+
 /* ---- shared-read graph ----------------------------------------------------- */
 /* A pair list: unique keys (a << 32 | b, a <= b) sorted ascending with int64
  * counts (and, for eq classes, the first emission position). */

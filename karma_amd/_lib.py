@@ -130,6 +130,13 @@ _SIGS = {
                           _i32, ctypes.c_double, ctypes.c_double, _u64, _i32, _c_p, _i32],
     "karma_umap_ab": [ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                       ctypes.POINTER(ctypes.c_double)],
+    "karma_graph_components": [_c_p, _c_p, _c_p, _i64, _i64, _i32, _c_p, _i32, _I64P],
+    "karma_spectral_apply": [_c_p, _c_p, _c_p, _c_p, _i64, _i64, _i32, _c_p, _i32, _c_p, _i32],
+    "karma_spectral_tile": [ctypes.POINTER(ctypes.c_int)] * 3,
+    "karma_spectral_jacobi": [_c_p, _i32, _c_p, _c_p],
+    "karma_spectral_last_ms": [ctypes.POINTER(ctypes.c_double)],
+    "karma_umap_spectral": [_c_p, _c_p, _c_p, _c_p, _i64, _i64, _i32, _i32, _u64, ctypes.c_double, _i32, _c_p, _c_p,
+                            _c_p, _c_p, _c_p, _i32, _c_p],
     "karma_graph_records": [_c_p, _c_p, _i64, _i64, _i32, _i32, _PP],
     "karma_graph_records_begin": [_c_p, _c_p, _i64, _i64, _i32, _i32, _PP],
     "karma_graph_records_end": [_c_p, _PP],
@@ -528,6 +535,13 @@ def mst_tile():
     """(query rows per block, candidate rows per step, columns staged at a time, most rounds) of karma_mreach_mst."""
     v = [ctypes.c_int(0) for _ in range(4)]
     call("karma_mst_tile", *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def spectral_tile():
+    """(rows per tile of the spectral solver's reordered block, guard columns, filter degree) (karma_spectral_tile)."""
+    v = [ctypes.c_int(0) for _ in range(3)]
+    call("karma_spectral_tile", *[ctypes.byref(x) for x in v])
     return tuple(x.value for x in v)
 
 

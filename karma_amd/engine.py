@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import call, ptr
+from .logs import logger
 
 KMODE_5P6 = _lib.KARMA_KMER_5P6
 
@@ -684,18 +685,135 @@ def umap_default_epochs(n):
     return 500 if n <= 10000 else 200
 
 
+def _csr_graph(graph, need_weights=True):
+    """(device, n, nnz, the three arrays) of a CSR graph given as numpy arrays or as DevBufs."""
+    indptr, indices = graph[0], graph[1]
+    weights = graph[2] if need_weights else None
+    parts = (indptr, indices, weights) if need_weights else (indptr, indices)
+    device = _on_device(*parts)
+    if not device and any(isinstance(x, _lib.DevBuf) for x in parts):
+        raise TypeError("the graph's arrays must all be numpy arrays or all be DevBufs")
+    n = (indptr.size if device else len(indptr)) - 1
+    nnz = indices.size if device else len(indices)
+    if need_weights and (weights.size if device else len(weights)) != nnz:
+        raise ValueError("indices and weights must have the same length")
+    return device, n, nnz, indptr, indices, weights
+
+
+def graph_components(graph, ctx=None, out_device=False):
+    """The connected components of a CSR graph read as undirected
+    (karma_graph_components): graph = (indptr, indices[, weights]), numpy
+    arrays or DevBufs; the weights are not looked at.  Returns (comp, n_comp):
+    comp int32[n], every vertex's smallest component member (a numpy array, or
+    a DevBuf with out_device=True)."""
+    device, n, nnz, indptr, indices, _ = _csr_graph(graph, need_weights=False)
+    if n < 1:
+        raise ValueError(f"need n >= 1, not {n}")
+    if ctx is None:
+        ctx = indptr.ctx if device else _lib.default_context()
+    pp, keep_p = _dev_or_host(indptr, np.int64)
+    pi, keep_i = _dev_or_host(indices, np.int32)
+    comp = _lib.DevBuf(ctx, (n,), np.int32) if out_device else np.empty(n, np.int32)
+    count = ctypes.c_int64(0)
+    call("karma_graph_components", ctx.h, pp, pi, n, nnz, 1 if device else 0,
+         ctypes.c_void_p(comp.ptr) if out_device else ptr(comp), 1 if out_device else 0, ctypes.byref(count))
+    return comp, count.value
+
+
+def spectral_apply(graph, x, ctx=None):
+    """S x for the block x (float64 (n, p), p <= 32, a numpy array) and the
+    normalised operator S = D^-1/2 W D^-1/2 of the CSR graph
+    (karma_spectral_apply; every bit defined by include/karma.h).  Returns
+    float64 (n, p)."""
+    device, n, nnz, indptr, indices, weights = _csr_graph(graph)
+    x = np.ascontiguousarray(x, np.float64)
+    if x.ndim != 2 or x.shape[0] != n or not 1 <= x.shape[1] <= 32:
+        raise ValueError(f"x must have shape ({n}, p) with 1 <= p <= 32, not {x.shape}")
+    if n < 2:
+        raise ValueError(f"need n >= 2, not {n}")
+    if ctx is None:
+        ctx = indptr.ctx if device else _lib.default_context()
+    pp, keep_p = _dev_or_host(indptr, np.int64)
+    pi, keep_i = _dev_or_host(indices, np.int32)
+    pw, keep_w = _dev_or_host(weights, np.float64)
+    out = np.empty_like(x)
+    call("karma_spectral_apply", ctx.h, pp, pi, pw, n, nnz, 1 if device else 0, ptr(x), x.shape[1], ptr(out), 0)
+    return out
+
+
+class SpectralStats:
+    """What umap_spectral(with_stats=True) returns beside y: vec, lam, res
+    (float64 (n, dim)), comp (int32[n]) and the counts of info."""
+
+    def __init__(self, vec, lam, res, comp, info):
+        self.vec, self.lam, self.res, self.comp = vec, lam, res, comp
+        self.components, self.not_converged, self.outer_rounds, self.applications = (int(v) for v in info)
+
+
+def umap_spectral(graph, n_components, seed, tol=1e-4, max_outer=100, ctx=None, out_device=False, with_stats=False):
+    """UMAP's spectral start of a symmetric CSR graph, component by component
+    (karma_umap_spectral; the contract is in include/karma.h): graph =
+    (indptr, indices, weights) as umap_graph returns them, numpy arrays or
+    DevBufs.  Returns y float64 (n, n_components) for umap_layout's init= (a
+    numpy array, or a DevBuf with out_device=True); with_stats=True returns
+    (y, SpectralStats).  tol: the residual |S v - theta v| below which a
+    component's eigenvectors count as converged (umap's eigsh tolerance);
+    max_outer: the outer rounds a component may take.  A component that does
+    not converge takes the random start on its rows and is counted in the
+    stats; it is not an error."""
+    device, n, nnz, indptr, indices, weights = _csr_graph(graph)
+    dim, seed, tol, max_outer = int(n_components), int(seed), float(tol), int(max_outer)
+    if n < 2:
+        raise ValueError(f"need n >= 2, not {n}")
+    if not 1 <= dim <= 16:
+        raise ValueError(f"need 1 <= n_components <= 16, not {dim}")
+    if not (np.isfinite(tol) and tol > 0):
+        raise ValueError(f"need tol finite and > 0, not {tol}")
+    if max_outer < 1:
+        raise ValueError(f"need max_outer >= 1, not {max_outer}")
+    if ctx is None:
+        ctx = indptr.ctx if device else _lib.default_context()
+    pp, keep_p = _dev_or_host(indptr, np.int64)
+    pi, keep_i = _dev_or_host(indices, np.int32)
+    pw, keep_w = _dev_or_host(weights, np.float64)
+
+    def make(shape, dtype):
+        return _lib.DevBuf(ctx, shape, dtype) if out_device else np.empty(shape, dtype)
+
+    def arg(buf):
+        return None if buf is None else (ctypes.c_void_p(buf.ptr) if out_device else ptr(buf))
+
+    y = make((n, dim), np.float64)
+    vec = lam = res = comp = None
+    if with_stats:
+        vec, lam, res = (make((n, dim), np.float64) for _ in range(3))
+        comp = make((n,), np.int32)
+    info = np.zeros(4, np.int64)
+    call("karma_umap_spectral", ctx.h, pp, pi, pw, n, nnz, 1 if device else 0, dim, ctypes.c_uint64(seed & (2**64 - 1)),
+         tol, max_outer, arg(y), arg(vec), arg(lam), arg(res), arg(comp), 1 if out_device else 0, ptr(info))
+    if info[1]:
+        logger.warning(f"Spectral initialisation: {int(info[1])} of {int(info[0])} graph components did not converge "
+                       f"within {max_outer} rounds; they start from random coordinates.")
+    return (y, SpectralStats(vec, lam, res, comp, info)) if with_stats else y
+
+
 def umap(x, n_neighbors=15, n_components=2, min_dist=0.1, spread=1.0, random_state=42, n_epochs=None, init=None,
          knn=None, ctx=None):
     """UMAP of the rows of the float64 matrix x (n, M) on the device: exact
     neighbour lists (knn_rows, or the (idx, dist) passed as knn=), the fuzzy
     graph (umap_graph), the curve (umap_ab) and the layout (umap_layout) from a
-    random start (or init=).  x: what knn_rows accepts, a DeviceProfile
-    included; the lists and the graph stay on the device.  n_epochs=None: 500
-    for n <= 10000, else 200.  Returns float64[n, n_components].  Every bit is
-    defined by include/karma.h; the result is not claimed to equal
-    umap-learn's coordinates (its layout is a racy parallel SGD with its own
-    generator)."""
+    random start (or init=: an array, or "spectral" for umap_spectral's start,
+    built on the device and handed over there).  x: what knn_rows accepts, a
+    DeviceProfile included; the lists and the graph stay on the device.
+    n_epochs=None: 500 for n <= 10000, else 200.  Returns float64[n,
+    n_components].  Every bit is defined by include/karma.h; the result is not
+    claimed to equal umap-learn's coordinates (its layout is a racy parallel
+    SGD with its own generator)."""
     host, _, n, _, _ = _knn_source(x)
+    if isinstance(init, str) and init not in ("spectral", "random"):
+        raise ValueError(f"init must be None, \"random\", \"spectral\" or an array, not {init!r}")
+    if isinstance(init, str) and init == "random":
+        init = None
     if ctx is None:
         ctx = x.ctx if host is None else _lib.default_context()
     own = []
@@ -717,6 +835,10 @@ def umap(x, n_neighbors=15, n_components=2, min_dist=0.1, spread=1.0, random_sta
         a, b = umap_ab(spread, min_dist)
         epochs = umap_default_epochs(n) if n_epochs is None else int(n_epochs)
         seed = 0 if random_state is None else int(random_state)
+        if isinstance(init, str):  # "spectral": the start is built where the graph lies and stays there
+            start = umap_spectral(graph, n_components, seed, ctx=ctx, out_device=True)
+            own.append(start)
+            return umap_layout(graph, n_components, a, b, epochs, seed, init=start, ctx=ctx).numpy()
         return umap_layout(graph, n_components, a, b, epochs, seed, init=init, ctx=ctx)
     finally:
         for buf in own:

@@ -132,7 +132,7 @@ class KmerClustering:
             fh.write("\t".join(str(v) for v in kwargs.values()) + "\n")
 
     def run(self, neighbors, components, dist, r_state, min_cluster_size, device_knn=False, device_hdbscan=False,
-            device_umap=False):
+            device_umap=False, umap_init="random"):
         """kmer.py:274-325.  The profile is computed on the GPU; UMAP/HDBSCAN
         are the reference's third-party dependencies and must be importable.
 
@@ -156,7 +156,17 @@ class KmerClustering:
         device (the lists come from there whether or not device_knn is set),
         and `umap` is not imported.  With device_hdbscan as well, neither
         package is imported.  Its coordinates are defined bit for bit by the
-        library's contract and are not claimed to equal umap-learn's."""
+        library's contract and are not claimed to equal umap-learn's.
+
+        umap_init (an addition; default "random": nothing changes):
+        "spectral" starts the device layout from engine.umap_spectral's
+        coordinates, as umap.UMAP's default init does; it needs
+        device_umap=True (ValueError otherwise: the umap-learn path takes its
+        own default)."""
+        if umap_init not in ("random", "spectral"):
+            raise ValueError(f"umap_init must be \"random\" or \"spectral\", not {umap_init!r}")
+        if umap_init == "spectral" and not device_umap:
+            raise ValueError("umap_init=\"spectral\" is the device layout's start: it needs device_umap=True")
         if os.path.isfile(self.output_file):
             logger.info(f"Read from previous calculation: {self.output_file}")
             self.__read_clusters()
@@ -193,7 +203,8 @@ class KmerClustering:
             logger.info("Dimension reduction with UMAP.")
             if device_umap:
                 try:
-                    reduced = engine.umap(kmer_profile, neighbors, components, dist, random_state=r_state)
+                    reduced = engine.umap(kmer_profile, neighbors, components, dist, random_state=r_state,
+                                          init="spectral" if umap_init == "spectral" else None)
                 finally:
                     kmer_profile.close()
             else:
